@@ -10,8 +10,10 @@ Multi-GPU: weak scaling — every rank owns an independent token-disjoint job
 
 Inputs are generated ON THE GPU by the product write path before the timed
 region; the timed region is gpuc_compact (file read -> H2D -> kernels -> D2H
--> file write). The cpu_baseline leg times the CPU oracle (kind "port") on a
-bounded sample at N=1.
+-> file write). A plain run sets up, warms up, times the K steps and prints
+one JSON result line. `--full` adds the cpu_baseline leg, which times the CPU
+oracle (kind "port") on a bounded sample at N=1. `--dump-outputs DIR` writes
+what the last timed step produced as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -68,6 +70,58 @@ def algorithmic_bytes(kernel, r):
     return in_unc
 
 
+DUMP_SAMPLE_BLOCK = 4096          # bytes per sampled block
+DUMP_SAMPLE_BYTES = 1 << 20       # sampled bytes per component file (4 MiB as float32)
+DUMP_SAMPLE_SEED = 0x5EED
+RESULT_COUNTERS = ["input_uncompressed_bytes", "output_uncompressed_bytes",
+                   "output_compressed_bytes", "partitions_in", "partitions_out",
+                   "rows_in", "rows_out"]
+
+
+def dump_outputs(dump_dir, out_dir, result):
+    """Write what the last timed step produced as <dump_dir>/<name>.npy.
+
+    A compaction's outputs are the sstable component files plus the result
+    counters. Each component file becomes a float32 array of its byte values:
+    whole when it fits in DUMP_SAMPLE_BYTES, else a fixed seeded sample of
+    DUMP_SAMPLE_BLOCK-byte blocks (offsets depend only on the file size).
+    Digest.crc32 — the writer's checksum over all of Data.db — is always whole,
+    so full-file equality of two builds is still visible through the sample.
+    `file_sizes.npy` (float64, files in sorted-name order) and `counters.npy`
+    (float64, RESULT_COUNTERS order) pin what the samples cannot.
+    Worst case 8 components x 4 MiB per output sstable, well under 64 MB.
+    """
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "counters.npy"),
+            np.array([float(result.get(k, 0)) for k in RESULT_COUNTERS], dtype=np.float64))
+    names = sorted(n for n in os.listdir(out_dir)
+                   if os.path.isfile(os.path.join(out_dir, n))) if os.path.isdir(out_dir) else []
+    # keep the total bounded when a job emits many sharded sstables
+    per_file = min(DUMP_SAMPLE_BYTES, (48 << 20) // 4 // max(1, len(names)))
+    n_blocks = max(1, per_file // DUMP_SAMPLE_BLOCK)
+    sizes = []
+    for name in names:
+        path = os.path.join(out_dir, name)
+        size = os.path.getsize(path)
+        sizes.append(float(size))
+        with open(path, "rb") as f:
+            if size <= n_blocks * DUMP_SAMPLE_BLOCK:
+                raw = f.read()
+            else:
+                total_blocks = (size + DUMP_SAMPLE_BLOCK - 1) // DUMP_SAMPLE_BLOCK
+                rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+                picks = np.sort(rng.choice(total_blocks, size=n_blocks, replace=False))
+                parts = []
+                for b in picks:
+                    f.seek(int(b) * DUMP_SAMPLE_BLOCK)
+                    parts.append(f.read(DUMP_SAMPLE_BLOCK))
+                raw = b"".join(parts)
+        np.save(os.path.join(dump_dir, name + ".npy"),
+                np.frombuffer(raw, dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(dump_dir, "file_sizes.npy"), np.array(sizes, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -90,7 +144,14 @@ def main():
     ap.add_argument("--shards", type=int, default=1,
                     help="n_output_shards per job (UCS-style sharded outputs; "
                          "2 shards run concurrently inside the library)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not need: "
+                         "the CPU-oracle baseline (cpu_baseline in the result line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU-oracle baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step produced "
+                         "(sstable component files, result counters) as DIR/<name>.npy")
     ap.add_argument("--snappy", action="store_true",
                     help="C3 codec: SnappyCompressor chunks end to end")
     ap.add_argument("--dry-run", action="store_true",
@@ -99,6 +160,8 @@ def main():
                          "generate/compact mocked — so the first real multi-GPU "
                          "run is not the first execution of this code")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -202,6 +265,11 @@ def main():
     for t in cleaners:
         t.join()
 
+    if args.dump_outputs:
+        # every rank owns an independent job: rank 0 writes DIR, others DIR/r<rank>
+        dump_dir = args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"r{rank}")
+        dump_outputs(dump_dir, os.path.join(dout, f"out-{args.steps - 1}"), last)
+
     my_bytes = float(last["input_uncompressed_bytes"] * args.steps)
     if dist:
         t = torch.tensor([elapsed])
@@ -241,9 +309,9 @@ def main():
         "traffic": traffic,
     }
 
-    # ---- CPU baseline: oracle compactor, bounded sample, 1 thread ----
+    # ---- CPU baseline (--full only): oracle compactor, bounded sample, 1 thread ----
     cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.dry_run:
         ob = oracle_bin()
         sd = os.path.join(args.dir, "cpu_sample")
         shutil.rmtree(sd, ignore_errors=True)
