@@ -48,6 +48,7 @@ class GpucJob(ctypes.Structure):
         ("cell_level_gc", ctypes.c_int32),
         ("n_output_shards", ctypes.c_int32),
         ("cancel_flag", ctypes.POINTER(ctypes.c_int32)),
+        ("output_chunk_length", ctypes.c_uint32),
     ]
 
 
@@ -107,6 +108,7 @@ class GpucGenSpec(ctypes.Structure):
         ("complex_del_pct", ctypes.c_uint32),
         ("bti", ctypes.c_int32),
         ("counter", ctypes.c_int32),
+        ("chunk_length", ctypes.c_uint32),
     ]
 
 
@@ -166,6 +168,13 @@ def load_library(path=None):
                                          ctypes.c_char_p, ctypes.c_int32,
                                          ctypes.c_char_p, ctypes.c_size_t]
         lib.gpuc_flush_table.restype = ctypes.c_int
+    if hasattr(lib, "gpuc_compress_buffer"):  # absent in frozen A/B probe builds
+        lib.gpuc_compress_buffer.argtypes = [
+            ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
+            ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+            ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+            ctypes.c_char_p, ctypes.c_size_t]
+        lib.gpuc_compress_buffer.restype = ctypes.c_int
     lib.gpuc_version.restype = ctypes.c_char_p
     lib.gpuc_device_count.restype = ctypes.c_int
     _lib = lib
@@ -295,6 +304,7 @@ class GpucFlushSchema(ctypes.Structure):
         ("stats_min_ts", ctypes.c_int64),
         ("stats_min_ldt", ctypes.c_int64),
         ("stats_min_ttl", ctypes.c_int32),
+        ("chunk_length", ctypes.c_uint32),
     ]
 
 
@@ -505,13 +515,16 @@ def _flush_table_parsed(S, parts, n_parts, output_base, device=0):
         raise GpuCompactError(f"gpuc_flush_table rc={rc}: {err.value.decode(errors='replace')}")
 
 
-def flush_table(memdump_path, output_base, device=0):
+def flush_table(memdump_path, output_base, device=0, chunk_length=0):
     """Full-schema memtable flush: marshal an oracle .memdump (the logical
     memtable content) through gpuc_flush_table. A real host would build the
-    same structs straight from its memtable."""
+    same structs straight from its memtable.
+    chunk_length: output chunk length in bytes (power of two, 1024..65536);
+    0 == 16 KiB."""
     with open(memdump_path, "rb") as f:
         data = f.read()
     S, parts, n_parts, bufs = _parse_memdump(data)
+    S.chunk_length = chunk_length
     _flush_table_parsed(S, parts, n_parts, output_base, device)
     del bufs
 
@@ -540,6 +553,30 @@ def verify(input_base, device=0):
         raise GpuCompactError(f"gpuc_verify rc={rc}: {err.value.decode(errors='replace')}")
 
 
+def compress_buffer(data, chunk_length=0, snappy=False, device=0):
+    """Chunk-compress `data` with the writer's own kernels (diagnostic).
+    Returns (image, offsets): the Data.db image (per chunk: payload, then
+    big-endian CRC32) and the CompressionInfo.db chunk offsets."""
+    lib = load_library()
+    data = bytes(data)
+    cl = chunk_length or 16384
+    n_max = (len(data) + cl - 1) // cl if cl > 0 else 0
+    # worst case per chunk: snappy's 32 + n + n/6, plus the CRC
+    cap = len(data) + len(data) // 6 + (n_max + 1) * 64 + 64
+    out = ctypes.create_string_buffer(cap)
+    offs = (ctypes.c_uint64 * max(n_max, 1))()
+    out_len = ctypes.c_uint64()
+    n = ctypes.c_uint32()
+    err = ctypes.create_string_buffer(256)
+    rc = lib.gpuc_compress_buffer(data, len(data), chunk_length, 1 if snappy else 0, device,
+                                  out, cap, ctypes.byref(out_len), offs, max(n_max, 1),
+                                  ctypes.byref(n), err, 256)
+    if rc != 0:
+        raise GpuCompactError(
+            f"gpuc_compress_buffer rc={rc}: {err.value.decode(errors='replace')}")
+    return out.raw[:out_len.value], list(offs[:n.value])
+
+
 def version():
     return load_library().gpuc_version().decode()
 
@@ -564,6 +601,7 @@ def compact(
     cell_level_gc=False,
     keep_ranges=None,
     invert_ranges=False,
+    output_chunk_length=0,
 ):
     """One compaction task (mirrors CompactionTask.runMayThrow's hot loop).
 
@@ -571,6 +609,8 @@ def compact(
     overlaps: list of (token_lo, token_hi, min_timestamp) for the purge
       evaluator (CompactionController.getPurgeEvaluator); None == no overlaps.
     token_range: (lo, hi) inclusive token shard restriction or None.
+    output_chunk_length: chunk length of the output in bytes (power of two,
+      1024..65536); 0 == the chunk length of input_bases[0].
     """
     lib = load_library()
     job = GpucJob()
@@ -628,6 +668,7 @@ def compact(
         job.tombstone_source_bases = tarr
         job.n_tomb_sources = len(tombstone_sources)
     job.cell_level_gc = 1 if cell_level_gc else 0
+    job.output_chunk_length = output_chunk_length
     res = GpucResult()
     rc = lib.gpuc_compact(ctypes.byref(job), ctypes.byref(res))
     if rc != 0:
@@ -716,8 +757,11 @@ def generate(
     base_ldt=1700000000,
     first_generation=1,
     device=0,
+    chunk_length=0,
 ):
-    """GPU-side synthetic sstable generation (shared contract: oracle/src/gen.h)."""
+    """GPU-side synthetic sstable generation (shared contract: oracle/src/gen.h).
+    chunk_length: output chunk length in bytes (power of two, 1024..65536);
+    0 == 16 KiB."""
     lib = load_library()
     spec = GpucGenSpec(
         seed=seed,
@@ -746,6 +790,7 @@ def generate(
         complex_del_pct=complex_del_pct,
         bti=1 if bti else 0,
         counter=1 if counter else 0,
+        chunk_length=chunk_length,
     )
     err = ctypes.create_string_buffer(256)
     rc = lib.gpuc_generate(ctypes.byref(spec), out_dir.encode(), err, 256)

@@ -20,7 +20,9 @@ constexpr int64_t NO_DELETION_TIME = INT64_MAX;
 constexpr uint32_t LDT_NONE_U32 = 0xFFFFFFFFu;
 constexpr int64_t TIMESTAMP_EPOCH = 1442880000000000LL;
 constexpr int64_t DELETION_TIME_EPOCH = 1442880000LL;
-constexpr uint32_t CHUNK_LEN = 16384;  // CompressionParams.DEFAULT_CHUNK_LENGTH
+// CompressionParams.DEFAULT_CHUNK_LENGTH: the default only — each sstable
+// carries its own chunk length (1..64 KiB, gpu_structs.h) as a runtime value
+constexpr uint32_t CHUNK_LEN = 16384;
 
 GPUC_HD inline int64_t ldt_long(uint32_t u) { return u == LDT_NONE_U32 ? NO_DELETION_TIME : (int64_t)u; }
 GPUC_HD inline uint32_t ldt_u32(int64_t l) { return l == NO_DELETION_TIME ? LDT_NONE_U32 : (uint32_t)l; }

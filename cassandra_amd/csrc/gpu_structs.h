@@ -1,6 +1,7 @@
 // PRODUCT — device-side data structures for the compaction pipeline.
 #pragma once
 #include <stdint.h>
+#include "codec.h"
 
 namespace gpuc {
 
@@ -200,7 +201,24 @@ struct OutStats {
     unsigned long long cpx_alloc;                    // output cpx-cell arena bump
 };
 
-constexpr uint32_t LZ4_SLOT = 16480;  // > 4 + LZ4_compressBound(16384), 16B aligned
-constexpr uint32_t SNP_SLOT = 19456;  // > snappy_max_compressed_length(16384)=19146, 16B aligned
+// Chunk lengths the codecs support: powers of two from 1 KiB to 64 KiB.
+// Above 64 KiB liblz4 leaves the byU16 table (at 65547 input bytes) and snappy
+// splits the input into several 64 KiB fragments — different algorithms.
+constexpr uint32_t MIN_CHUNK_LEN = 1024;
+constexpr uint32_t MAX_CHUNK_LEN = 65536;
+GPUC_HD constexpr bool chunk_len_pow2(uint32_t len) { return len && !(len & (len - 1)); }
+GPUC_HD constexpr bool chunk_len_supported(uint32_t len) {
+    return chunk_len_pow2(len) && len >= MIN_CHUNK_LEN && len <= MAX_CHUNK_LEN;
+}
+// largest valid chunk payload: 4-byte LE length + LZ4_compressBound(len) /
+// snappy_max_compressed_length(len). The decoders refuse longer frames.
+GPUC_HD constexpr uint32_t lz4_max_comp(uint32_t len) { return 4 + len + len / 255 + 16; }
+GPUC_HD constexpr uint32_t snp_max_comp(uint32_t len) { return 32 + len + len / 6; }
+// compressor output slot strides (16 B / 512 B aligned)
+GPUC_HD constexpr uint32_t lz4_slot_stride(uint32_t len) { return (lz4_max_comp(len) + 15u) & ~15u; }
+GPUC_HD constexpr uint32_t snp_slot_stride(uint32_t len) { return (snp_max_comp(len) + 511u) & ~511u; }
+constexpr uint32_t LZ4_SLOT = lz4_slot_stride(CHUNK_LEN);  // 16480
+constexpr uint32_t SNP_SLOT = snp_slot_stride(CHUNK_LEN);  // 19456
+static_assert(LZ4_SLOT == 16480 && SNP_SLOT == 19456, "16 KiB slot strides");
 
 }  // namespace gpuc

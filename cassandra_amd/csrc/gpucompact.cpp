@@ -188,12 +188,32 @@ static void write_file(const std::string& path, const uint8_t* p, size_t n) {
 // ---------------------------------------------------------------------------
 // component parsing (input side)
 // ---------------------------------------------------------------------------
+// typed failures the C ABI maps to GPUC_ERR_UNSUPPORTED / GPUC_ERR_FORMAT
+struct unsupported_error : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+struct format_error : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+static const char* const CHUNK_LEN_WHY =
+    " (supported: powers of two from 1 KiB to 64 KiB; above 64 KiB liblz4 leaves its byU16 "
+    "table and snappy splits into several 64 KiB fragments)";
+// a chunk length handed in as an ARGUMENT (0 == caller's default)
+static uint32_t checked_chunk_len_arg(uint32_t len, uint32_t dflt) {
+    if (len == 0) return dflt;
+    if (!chunk_len_supported(len))
+        throw unsupported_error("unsupported chunk_length " + std::to_string(len) + CHUNK_LEN_WHY);
+    return len;
+}
+
 struct HCompressionInfo {
     uint32_t chunk_len = 16384;
     uint32_t max_compressed = 0x7FFFFFFF;
     uint64_t data_len = 0;
     bool snappy = false;  // SnappyCompressor (else LZ4Compressor)
     std::vector<uint64_t> offsets;
+    // decoder sanity bound for this input's frames (gpu_structs.h)
+    uint32_t max_comp() const { return snappy ? snp_max_comp(chunk_len) : lz4_max_comp(chunk_len); }
 };
 static HCompressionInfo parse_compression_info(const bytes& b) {
     HReader r(b);
@@ -210,9 +230,16 @@ static HCompressionInfo parse_compression_info(const bytes& b) {
     ci.max_compressed = r.be32();
     ci.data_len = r.be64();
     uint32_t n = r.be32();
+    // checked before the offset table is even read: nothing downstream (and
+    // no kernel) ever sees a length the codecs were not built for
+    if (!chunk_len_pow2(ci.chunk_len))
+        throw format_error("CompressionInfo.db: chunk_length " + std::to_string(ci.chunk_len) +
+                           " is not a power of two");
+    if (!chunk_len_supported(ci.chunk_len))
+        throw unsupported_error("unsupported chunk_length " + std::to_string(ci.chunk_len) +
+                                CHUNK_LEN_WHY);
     ci.offsets.resize(n);
     for (uint32_t i = 0; i < n; i++) ci.offsets[i] = r.be64();
-    if (ci.chunk_len != CHUNK_LEN) throw std::runtime_error("unsupported chunk_length (16 KiB only in round 1)");
     return ci;
 }
 
@@ -992,6 +1019,23 @@ static void build_bti_from_index_image(const uint8_t* idx, uint64_t idx_len, uin
     *rows_out = std::move(rows_file);
 }
 
+// The one place chunk-compress kernels are launched (sstable writer and
+// gpuc_compress_buffer): m chunks of chunk_len bytes (last one short) from
+// d_data -> payload slots of `stride` bytes + per-chunk size and CRC32.
+static void launch_chunk_compress(bool snappy, const uint8_t* d_data, uint64_t data_len,
+                                  uint8_t* d_slots, uint32_t* d_csize, uint32_t* d_ccrc,
+                                  uint32_t m, uint32_t chunk_len, uint32_t stride,
+                                  hipStream_t stream) {
+    if (snappy)
+        hipLaunchKernelGGL(k_snappy_compress_chunks, dim3(m), dim3(WAVE), 0, stream, d_data,
+                           data_len, d_slots, d_csize, d_ccrc, m, (const uint32_t*)g_crc256,
+                           g_snp_off, g_snp_off_n, chunk_len, stride);
+    else
+        hipLaunchKernelGGL(k_lz4_compress_wave_t<false>, dim3(m), dim3(WAVE), 0, stream, d_data,
+                           data_len, d_slots, d_csize, d_ccrc, m, (const uint32_t*)g_crc256,
+                           (uint32_t*)nullptr, chunk_len, stride);
+}
+
 static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfColsBuf& rows,
                                            uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
                                            DevBuf& d_tomb, uint32_t tomb_cap,
@@ -1001,9 +1045,14 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
                                            const std::vector<std::pair<bytes, std::string>>& regular_cols,
                                            const std::vector<std::pair<bytes, std::string>>& static_cols,
                                            hipStream_t stream, int wslot = 0,
-                                           bool snappy_out = false, bool bti_out = false) {
+                                           bool snappy_out = false, bool bti_out = false,
+                                           uint32_t out_chunk_len = CHUNK_LEN) {
     WriteDeviceOut w;
-    const uint32_t SLOT_STRIDE = snappy_out ? SNP_SLOT : LZ4_SLOT;
+    if (!chunk_len_supported(out_chunk_len))
+        throw unsupported_error("unsupported output chunk_length " + std::to_string(out_chunk_len) +
+                                CHUNK_LEN_WHY);
+    const uint32_t OCL = out_chunk_len;
+    const uint32_t SLOT_STRIDE = snappy_out ? snp_slot_stride(OCL) : lz4_slot_stride(OCL);
     TR("wsd: enter");
     static const std::vector<int64_t> ps_off_h = est_hist_offsets(155);
     static const std::vector<int64_t> ch_off_h = est_hist_offsets(118);
@@ -1122,8 +1171,10 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     // and host writer threads pwrite each drained slab into Data.db at its
     // final offset. Output I/O therefore rides under the compress kernel
     // instead of following it.
-    uint32_t n_chunks = (uint32_t)((total_unc + CHUNK_LEN - 1) / CHUNK_LEN);
-    const uint32_t SLAB = 32768;  // 512 MiB uncompressed per slab
+    if ((total_unc + OCL - 1) / OCL > 0xFFFFFFFFull)
+        throw std::runtime_error("output too large for this chunk_length");
+    uint32_t n_chunks = (uint32_t)((total_unc + OCL - 1) / OCL);
+    const uint32_t SLAB = (512u << 20) / OCL;  // 512 MiB uncompressed per slab (32768 x 16 KiB)
     uint32_t n_slabs = n_chunks ? (n_chunks + SLAB - 1) / SLAB : 0;
     DevBuf d_slots, d_csize, d_ccrc;
     d_slots.alloc((uint64_t)n_chunks * SLOT_STRIDE + 16);
@@ -1144,7 +1195,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         if (NSEG > 1) {
             // issue the serialize segments covering this slab's bytes AHEAD
             // of it on the same in-order stream (ordering IS the dependency)
-            uint64_t slab_end = std::min<uint64_t>((uint64_t)(cb + m) * CHUNK_LEN, total_unc);
+            uint64_t slab_end = std::min<uint64_t>((uint64_t)(cb + m) * OCL, total_unc);
             while (seg_issued < NSEG && (seg_issued ? seg_end_byte[seg_issued - 1] : 0) < slab_end)
                 launch_serialize_seg(seg_issued++);
             if (seg_issued == NSEG) {
@@ -1154,20 +1205,11 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         }
         // all kernel arguments shift uniformly per chunk, so a slab launch is
         // just base-offset pointers with a local chunk count
-        if (snappy_out)
-            hipLaunchKernelGGL(k_snappy_compress_chunks, dim3(m), dim3(WAVE), 0, stream,
-                               d_out_data.as<uint8_t>() + (uint64_t)cb * CHUNK_LEN,
-                               total_unc - (uint64_t)cb * CHUNK_LEN,
-                               d_slots.as<uint8_t>() + (uint64_t)cb * SNP_SLOT,
-                               d_csize.as<uint32_t>() + cb, d_ccrc.as<uint32_t>() + cb, m,
-                               (const uint32_t*)g_crc256, g_snp_off, g_snp_off_n);
-        else
-            hipLaunchKernelGGL(k_lz4_compress_wave_t<false>, dim3(m), dim3(WAVE), 0, stream,
-                           d_out_data.as<uint8_t>() + (uint64_t)cb * CHUNK_LEN,
-                           total_unc - (uint64_t)cb * CHUNK_LEN,
-                           d_slots.as<uint8_t>() + (uint64_t)cb * LZ4_SLOT,
-                           d_csize.as<uint32_t>() + cb, d_ccrc.as<uint32_t>() + cb, m,
-                           (const uint32_t*)g_crc256);
+        launch_chunk_compress(snappy_out, d_out_data.as<uint8_t>() + (uint64_t)cb * OCL,
+                              total_unc - (uint64_t)cb * OCL,
+                              d_slots.as<uint8_t>() + (uint64_t)cb * SLOT_STRIDE,
+                              d_csize.as<uint32_t>() + cb, d_ccrc.as<uint32_t>() + cb, m, OCL,
+                              SLOT_STRIDE, stream);
         HIP_CHECK(hipEventCreate(&ev_c[i]));
         HIP_CHECK(hipEventRecord(ev_c[i], stream));
     }
@@ -1489,7 +1531,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
             put_be16(ci, (uint16_t)algo.size());
             ci.insert(ci.end(), algo.begin(), algo.end());
             put_be32(ci, 0);
-            put_be32(ci, CHUNK_LEN);
+            put_be32(ci, OCL);
             put_be32(ci, 0x7FFFFFFF);
             put_be64(ci, total_unc);
             put_be32(ci, n_chunks);
@@ -1573,6 +1615,7 @@ struct CompactSetup {
     std::vector<std::string> in_bases;
     std::vector<bytes> index_data;
     std::vector<HCompressionInfo> cinfos;
+    uint32_t out_chunk_len = CHUNK_LEN;  // resolved from the job / cinfos[0]
     std::vector<HStatistics> stats;
     std::vector<uint64_t> generations;
     std::vector<std::vector<uint64_t>> positions;   // n_parts+1 absolute offsets
@@ -1656,8 +1699,9 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             win_n[s] = bhi - blo;
             data_lo[s] = positions[s][blo];
             data_hi[s] = positions[s][bhi];
-            uint64_t c_lo = data_lo[s] / CHUNK_LEN;
-            uint64_t c_hi = (data_hi[s] + CHUNK_LEN - 1) / CHUNK_LEN;
+            const uint64_t icl = su.cinfos[s].chunk_len;  // per input
+            uint64_t c_lo = data_lo[s] / icl;
+            uint64_t c_hi = (data_hi[s] + icl - 1) / icl;
             uint64_t n_chunks_file = su.cinfos[s].offsets.size();
             if (c_hi > n_chunks_file) c_hi = n_chunks_file;
             if (win_n[s] == 0) { c_lo = c_hi = 0; }
@@ -1710,7 +1754,8 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             auto& ci = cinfos[s];
             uint64_t n_chunks_file = ci.offsets.size();
             uint64_t c_lo = win_chunk_lo[s];
-            uint64_t c_hi = win_n[s] ? (data_hi[s] + CHUNK_LEN - 1) / CHUNK_LEN : c_lo;
+            const uint64_t icl = ci.chunk_len;  // inputs of one job may differ
+            uint64_t c_hi = win_n[s] ? (data_hi[s] + icl - 1) / icl : c_lo;
             if (c_hi > n_chunks_file) c_hi = n_chunks_file;
             uint64_t n_wchunks = c_hi - c_lo;
             d_comp[s].alloc(comp_sz[s] ? comp_sz[s] : 1);
@@ -1741,10 +1786,10 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                                              hipMemcpyHostToDevice, copy_stream));
             }
             ms_read_data = wall() - tr + ms_read_data;
-            d_data[s].alloc(n_wchunks * (uint64_t)CHUNK_LEN + 16);
+            d_data[s].alloc(n_wchunks * icl + 16);
             // positions stay ABSOLUTE: the decompressed window is addressed
             // through a virtual origin so partition offsets need no rewrite
-            vbase[s] = d_data[s].as<uint8_t>() - c_lo * (uint64_t)CHUNK_LEN;
+            vbase[s] = d_data[s].as<uint8_t>() - c_lo * icl;
             uint64_t n_wpos = (uint64_t)win_n[s] + 1;
             d_pos[s].alloc(n_wpos * 8);
             HIP_CHECK(hipMemcpyAsync(d_pos[s].p, positions[s].data() + win_blo[s], n_wpos * 8,
@@ -1756,9 +1801,9 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 uint64_t end = c + 1 < n_chunks_file ? ci.offsets[c + 1] : su.comp_file_sz[s];
                 ChunkDesc cd;
                 cd.comp = d_comp[s].as<uint8_t>() + (off - win_comp_lo[s]);
-                cd.out = d_data[s].as<uint8_t>() + (c - c_lo) * (uint64_t)CHUNK_LEN;
+                cd.out = d_data[s].as<uint8_t>() + (c - c_lo) * icl;
                 cd.comp_len = (uint32_t)(end - off - 4);
-                cd.out_len = (uint32_t)std::min<uint64_t>(CHUNK_LEN, ci.data_len - c * (uint64_t)CHUNK_LEN);
+                cd.out_len = (uint32_t)std::min<uint64_t>(icl, ci.data_len - c * icl);
                 chunks.push_back(cd);
             }
             d_chunks_s[s].alloc(chunks.size() * sizeof(ChunkDesc) + 16);
@@ -1774,11 +1819,12 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                                        dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
                                        stream, d_chunks_s[s].as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
                                        d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                       (uint8_t*)nullptr);
+                                       (uint8_t*)nullptr, ci.max_comp());
                 else
                     hipLaunchKernelGGL(k_lz4_decompress_wave, dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
                                        stream, d_chunks_s[s].as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                                       d_error.as<unsigned long long>(), (const uint32_t*)g_crc256);
+                                       d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
+                                       (uint8_t*)nullptr, ci.max_comp());
             }
         }
         {
@@ -2331,7 +2377,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                                                 tomb_cap, out_base_str, stats[0].key_type,
                                                 stats[0].clustering_types, stats[0].regular_cols,
                                                 stats[0].static_cols, stream, wslot,
-                                                su.cinfos[0].snappy, su.bti);
+                                                su.cinfos[0].snappy, su.bti, su.out_chunk_len);
         TR("writer done");
         {
             OutStats hst;
@@ -2450,6 +2496,7 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
     {
         std::vector<std::thread> mth;
         std::vector<std::string> merr(k);
+        std::vector<int> mkind(k, 0);  // 1 unsupported, 2 format (keeps the ABI code)
         for (int s = 0; s < k; s++) {
             su.in_bases[s] = s < su.k_data ? job->input_bases[s]
                                            : job->tombstone_source_bases[s - su.k_data];
@@ -2482,12 +2529,18 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
                     su.cinfos[s] = parse_compression_info(read_file(base + "-CompressionInfo.db"));
                     su.stats[s] = parse_statistics(read_file(base + "-Statistics.db"));
                     if (!preread_full) su.comp_file_sz[s] = file_size_of(base + "-Data.db");
+                } catch (const unsupported_error& e) { merr[s] = e.what(); mkind[s] = 1;
+                } catch (const format_error& e) { merr[s] = e.what(); mkind[s] = 2;
                 } catch (const std::exception& e) { merr[s] = e.what(); }
             });
         }
         for (auto& t : mth) t.join();
         for (int s = 0; s < k; s++)
-            if (!merr[s].empty()) throw std::runtime_error(merr[s]);
+            if (!merr[s].empty()) {
+                if (mkind[s] == 1) throw unsupported_error(merr[s]);
+                if (mkind[s] == 2) throw format_error(merr[s]);
+                throw std::runtime_error(merr[s]);
+            }
     }
     for (int s = 0; s < k; s++) {
         const std::string& base = su.in_bases[s];
@@ -2602,10 +2655,15 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
             set_err(res->error, sizeof(res->error), "n_inputs (+ tombstone sources) must be 1..64");
             return GPUC_ERR_UNSUPPORTED;
         }
+        // argument check first: a bad output length never reads a byte
+        (void)checked_chunk_len_arg(job->output_chunk_length, CHUNK_LEN);
         double t0 = wall();
         int S_pre = job->n_output_shards > 1 ? job->n_output_shards : 1;
         CompactSetup su;
         compact_setup(job, su, S_pre == 1);
+        // 0 == the chunk length of input_bases[0] (what the reference
+        // compactor does when the table params are unchanged)
+        su.out_chunk_len = checked_chunk_len_arg(job->output_chunk_length, su.cinfos[0].chunk_len);
         res->ms_read_io = wall() - t0;
         TR("meta+index parsed");
         for (int s = 0; s < su.k_data; s++)
@@ -2739,6 +2797,14 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
         set_err(res->error, sizeof(res->error), e.what());
         res->ms_total = wall() - t_start_all;
         return GPUC_ERR_CANCELLED;
+    } catch (const unsupported_error& e) {
+        set_err(res->error, sizeof(res->error), e.what());
+        res->ms_total = wall() - t_start_all;
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const format_error& e) {
+        set_err(res->error, sizeof(res->error), e.what());
+        res->ms_total = wall() - t_start_all;
+        return GPUC_ERR_FORMAT;
     } catch (const std::exception& e) {
         set_err(res->error, sizeof(res->error), e.what());
         res->ms_total = wall() - t_start_all;
@@ -2808,9 +2874,9 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
             uint64_t end = c + 1 < ci.offsets.size() ? ci.offsets[c + 1] : comp_sz;
             ChunkDesc cd;
             cd.comp = d_comp.as<uint8_t>() + off;
-            cd.out = d_data.as<uint8_t>() + c * (uint64_t)CHUNK_LEN;
+            cd.out = d_data.as<uint8_t>() + c * (uint64_t)ci.chunk_len;
             cd.comp_len = (uint32_t)(end - off - 4);
-            cd.out_len = (uint32_t)std::min<uint64_t>(CHUNK_LEN, ci.data_len - c * (uint64_t)CHUNK_LEN);
+            cd.out_len = (uint32_t)std::min<uint64_t>(ci.chunk_len, ci.data_len - c * (uint64_t)ci.chunk_len);
             chunks.push_back(cd);
         }
         d_chunks.alloc(chunks.size() * sizeof(ChunkDesc) + 16);
@@ -2824,11 +2890,12 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
                                    dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
                                    stream, d_chunks.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
                                    d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                   (uint8_t*)nullptr);
+                                   (uint8_t*)nullptr, ci.max_comp());
             else
                 hipLaunchKernelGGL(k_lz4_decompress_wave, dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
                                stream, d_chunks.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                               d_error.as<unsigned long long>(), (const uint32_t*)g_crc256);
+                               d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
+                               (uint8_t*)nullptr, ci.max_comp());
         {
             unsigned long long e = 0;
             HIP_CHECK(hipStreamSynchronize(stream));
@@ -2933,6 +3000,9 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         }
         HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
     } catch (const std::exception& e) {
         set_err(error, error_len, e.what());
         return GPUC_ERR_FORMAT;
@@ -2979,9 +3049,9 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
             uint64_t end = c + 1 < n_chunks ? ci.offsets[c + 1] : comp_sz;
             ChunkDesc cd;
             cd.comp = d_comp.as<uint8_t>() + off;
-            cd.out = d_data.as<uint8_t>() + c * (uint64_t)CHUNK_LEN;
+            cd.out = d_data.as<uint8_t>() + c * (uint64_t)ci.chunk_len;
             cd.comp_len = (uint32_t)(end - off - 4);
-            cd.out_len = (uint32_t)std::min<uint64_t>(CHUNK_LEN, ci.data_len - c * (uint64_t)CHUNK_LEN);
+            cd.out_len = (uint32_t)std::min<uint64_t>(ci.chunk_len, ci.data_len - c * (uint64_t)ci.chunk_len);
             chunks.push_back(cd);
         }
         d_chunksb.alloc(chunks.size() * sizeof(ChunkDesc) + 16);
@@ -2993,12 +3063,12 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
                                    dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
                                    stream, d_chunksb.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
                                    d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                   d_bad.as<uint8_t>());
+                                   d_bad.as<uint8_t>(), ci.max_comp());
             else
                 hipLaunchKernelGGL(k_lz4_decompress_wave, dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
                                stream, d_chunksb.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
                                d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                               d_bad.as<uint8_t>());
+                               d_bad.as<uint8_t>(), ci.max_comp());
         std::vector<uint8_t> bad(n_chunks);
         HIP_CHECK(hipStreamSynchronize(stream));
         if (n_chunks)
@@ -3007,8 +3077,8 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         // kept partitions: all overlapped chunks clean
         std::vector<uint64_t> kpos, kend;
         for (uint64_t i = 0; i < n_parts; i++) {
-            uint64_t c0 = positions[i] / CHUNK_LEN;
-            uint64_t c1 = (positions[i + 1] + CHUNK_LEN - 1) / CHUNK_LEN;
+            uint64_t c0 = positions[i] / ci.chunk_len;
+            uint64_t c1 = (positions[i + 1] + ci.chunk_len - 1) / ci.chunk_len;
             bool ok = true;
             for (uint64_t c = c0; c < c1 && c < n_chunks; c++)
                 if (bad[c]) ok = false;
@@ -3209,9 +3279,15 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         sp2.hs.min_ttl = st.min_ttl == INT32_MAX ? 0 : st.min_ttl;
         write_sstable_device(opb, out_rows, n_groups, sp2, d_stats, d_tomb, tomb_cap, output_base,
                              st.key_type, st.clustering_types, st.regular_cols, st.static_cols,
-                             stream, 0, ci.snappy);
+                             stream, 0, ci.snappy, false, ci.chunk_len);
         HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const format_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_FORMAT;
     } catch (const std::exception& e) {
         set_err(error, error_len, e.what());
         return GPUC_ERR_INTERNAL;
@@ -3344,6 +3420,12 @@ extern "C" int gpuc_flush(const gpuc_flush_rows* rows, const char* output_base,
                              std::vector<std::pair<bytes, std::string>>{}, stream);
         HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const format_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_FORMAT;
     } catch (const std::exception& e) {
         set_err(error, error_len, e.what());
         return GPUC_ERR_INTERNAL;
@@ -3418,6 +3500,7 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         if (!schema || !parts || n_parts == 0) throw std::runtime_error("no partitions");
         const gpuc_flush_schema& S = *schema;
+        (void)checked_chunk_len_arg(S.chunk_length, CHUNK_LEN);  // before any work
         if (S.n_cols == 0 || S.n_cols + S.n_static > 63)
             throw std::runtime_error("1..63 columns supported");
         if (S.n_cpx > 1) throw std::runtime_error("at most one complex column");
@@ -3815,9 +3898,16 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         init_outstats(d_stats, stream);
         write_sstable_device(opb, urows, n_parts, sp, d_stats, d_tomb, tomb_cap, output_base,
                              key_type, ck_types, regular_cols, static_cols, stream, 0,
-                             S.snappy != 0, S.bti != 0);
+                             S.snappy != 0, S.bti != 0,
+                             checked_chunk_len_arg(S.chunk_length, CHUNK_LEN));
         HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const format_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_FORMAT;
     } catch (const std::exception& e) {
         set_err(error, error_len, e.what());
         return GPUC_ERR_INTERNAL;
@@ -3843,6 +3933,7 @@ extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t
 extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* error, size_t error_len) {
     try {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
+        (void)checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN);  // before any work
         HIP_CHECK(hipSetDevice(spec->device));
         hipStream_t stream;
         HIP_CHECK(hipStreamCreate(&stream));
@@ -4018,13 +4109,88 @@ extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* e
                                  std::vector<std::string>(
                                      gen_nck, gp.ck_text ? "org.apache.cassandra.db.marshal.UTF8Type"
                                                          : "org.apache.cassandra.db.marshal.LongType"),
-                                 cols, scols, stream, 0, spec->snappy != 0, spec->bti != 0);
+                                 cols, scols, stream, 0, spec->snappy != 0, spec->bti != 0,
+                                 checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN));
         }
         HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const format_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_FORMAT;
     } catch (const std::exception& e) {
         set_err(error, error_len, e.what());
         return GPUC_ERR_INTERNAL;
     }
 }
 
+
+// Diagnostic: chunk-compress a host buffer with the writer's own launch
+// (launch_chunk_compress + k_chunk_gather) and hand back the Data.db image.
+extern "C" int gpuc_compress_buffer(const uint8_t* data, uint64_t len, uint32_t chunk_length,
+                                    int32_t snappy, int32_t device, uint8_t* out,
+                                    uint64_t out_cap, uint64_t* out_len, uint64_t* offsets,
+                                    uint32_t offsets_cap, uint32_t* n_chunks_out, char* error,
+                                    size_t error_len) {
+    try {
+        if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
+        const uint32_t cl = checked_chunk_len_arg(chunk_length, CHUNK_LEN);
+        if (!data && len) throw unsupported_error("null data");
+        if ((len + cl - 1) / cl > 0x7FFFFFFFull) throw unsupported_error("buffer too large");
+        const uint32_t n_chunks = (uint32_t)((len + cl - 1) / cl);
+        if (n_chunks > offsets_cap) throw unsupported_error("offsets_cap too small");
+        HIP_CHECK(hipSetDevice(device));
+        hipStream_t stream;
+        HIP_CHECK(hipStreamCreate(&stream));
+        ensure_crc_tables(stream);
+        const uint32_t stride = snappy ? snp_slot_stride(cl) : lz4_slot_stride(cl);
+        uint64_t total = 0;
+        if (n_chunks) {
+            DevBuf d_in, d_slots, d_csize, d_ccrc, d_foff, d_gat;
+            d_in.alloc(len);
+            d_slots.alloc((uint64_t)n_chunks * stride + 16);
+            d_csize.alloc((uint64_t)n_chunks * 4 + 16);
+            d_ccrc.alloc((uint64_t)n_chunks * 4 + 16);
+            HIP_CHECK(hipMemcpyAsync(d_in.p, data, len, hipMemcpyHostToDevice, stream));
+            launch_chunk_compress(snappy != 0, d_in.as<uint8_t>(), len, d_slots.as<uint8_t>(),
+                                  d_csize.as<uint32_t>(), d_ccrc.as<uint32_t>(), n_chunks, cl,
+                                  stride, stream);
+            std::vector<uint32_t> cs(n_chunks);
+            HIP_CHECK(hipMemcpyAsync(cs.data(), d_csize.p, (uint64_t)n_chunks * 4,
+                                     hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+            std::vector<uint64_t> fo(n_chunks);
+            uint64_t acc = 0;
+            for (uint32_t c = 0; c < n_chunks; c++) {
+                if (cs[c] > stride) throw std::runtime_error("compressed chunk exceeds its slot");
+                fo[c] = acc;
+                offsets[c] = acc + (uint64_t)c * 4;  // CompressionInfo.db offsets
+                acc += cs[c];
+            }
+            total = acc + (uint64_t)n_chunks * 4;
+            if (total > out_cap) throw unsupported_error("out_cap too small");
+            d_foff.alloc((uint64_t)n_chunks * 8);
+            d_gat.alloc(total);
+            HIP_CHECK(hipMemcpyAsync(d_foff.p, fo.data(), (uint64_t)n_chunks * 8,
+                                     hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(k_chunk_gather, dim3(n_chunks), dim3(WAVE), 0, stream,
+                               d_slots.as<uint8_t>(), d_csize.as<uint32_t>(),
+                               d_ccrc.as<uint32_t>(), d_foff.as<uint64_t>(), d_gat.as<uint8_t>(),
+                               n_chunks, stride);
+            HIP_CHECK(hipMemcpyAsync(out, d_gat.p, total, hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        if (out_len) *out_len = total;
+        if (n_chunks_out) *n_chunks_out = n_chunks;
+        HIP_CHECK(hipStreamDestroy(stream));
+        return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const std::exception& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_INTERNAL;
+    }
+}

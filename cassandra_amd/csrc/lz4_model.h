@@ -1,7 +1,7 @@
 // PRODUCT — bit-exact restatement of LZ4_compress_default (liblz4 1.9.3,
 // byU16 strategy: input < 64 KB, acceleration 1) as a single-thread routine
 // compilable as both host and HIP device code. The GPU chunk-compress kernel
-// runs this per 16 KiB chunk (one per wave; lane 0 drives control flow, the
+// runs this per chunk of up to 64 KiB (one per wave; lane 0 drives control flow, the
 // wave assists bulk compares/copies in the .hip wrapper).
 //
 // The reference's compression bytes come from lz4-java 1.8.0, which bundles
@@ -80,7 +80,8 @@ LZ4M_HD static inline unsigned lz4m_count(const uint8_t* pIn, const uint8_t* pMa
 // noDict, noDictIssue, acceleration=1) — lz4.c:807-1028, restated for the
 // byU16/noDict/notLimited path only. `table` is caller-provided u16[8192],
 // zero-initialised (LZ4_prepareTable memsets for a fresh state).
-// Returns compressed size. srcSize must be >= 1 and < 65536 (byU16 regime)
+// Returns compressed size. srcSize must be >= 1 and <= 65536 (liblz4 stays in
+// the byU16 regime below 65547 bytes; positions up to 65535 fit the table)
 // and dst must have LZ4_compressBound(srcSize) capacity.
 LZ4M_HD static inline int lz4m_compress(const uint8_t* src, int srcSize, uint8_t* dst,
                                         uint16_t* table) {

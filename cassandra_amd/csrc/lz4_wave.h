@@ -49,7 +49,7 @@ __global__ void k_probe_lds_order(unsigned int* out) {
 }
 
 // ---------------------------------------------------------------------------
-// wave-cooperative compress: one wave per 16 KiB chunk
+// wave-cooperative compress: one wave per chunk (1..64 KiB)
 // s_chunk: staged input; s_table: u16[8192] zeroed; dst: global output (after
 // the caller-written 4-byte LE header). Returns compressed size via lane 0.
 // ---------------------------------------------------------------------------
@@ -420,15 +420,22 @@ __global__ void __launch_bounds__(WAVE) k_lz4_compress_wave_t(const uint8_t* dat
                                                               uint8_t* slots, uint32_t* csize,
                                                               uint32_t* ccrc, uint32_t n_chunks,
                                                               const uint32_t* crc_table,
-                                                              uint32_t* dbg = nullptr) {
+                                                              uint32_t* dbg = nullptr,
+                                                              uint32_t chunk_len = CHUNK_LEN,
+                                                              uint32_t slot_stride = LZ4_SLOT) {
+    // chunk_len / slot_stride are launch-uniform (SGPR) values: 1..64 KiB
+    // power-of-two chunks, stride >= lz4_slot_stride(chunk_len). The byU16
+    // table is 16 KiB of LDS at every supported length.
     __shared__ uint16_t s_table[LZ4M_HASHTABLESIZE_U16];
     uint32_t c = blockIdx.x;
     if (c >= n_chunks) return;
     int lane = threadIdx.x;
-    uint64_t off = (uint64_t)c * CHUNK_LEN;
-    uint32_t len = (uint32_t)min((uint64_t)CHUNK_LEN, data_len - off);
+    uint64_t off = (uint64_t)c * chunk_len;
+    uint32_t len = (uint32_t)min((uint64_t)chunk_len, data_len - off);
     const uint8_t* src;
     if constexpr (STAGE_LDS) {
+        // LDS-staged variant (not on the product path): 16 KiB chunks only
+        if (chunk_len != CHUNK_LEN) return;
         __shared__ uint8_t s_chunk[CHUNK_LEN];
         for (uint32_t i = lane * 4; i + 4 <= len; i += WAVE * 4)
             *(uint32_t*)&s_chunk[i] = *(const uint32_t*)((const uint8_t*)data + off + i);
@@ -439,7 +446,7 @@ __global__ void __launch_bounds__(WAVE) k_lz4_compress_wave_t(const uint8_t* dat
     }
     for (int i = lane; i < LZ4M_HASHTABLESIZE_U16; i += WAVE) s_table[i] = 0;
     __syncthreads();
-    uint8_t* dst = slots + (uint64_t)c * LZ4_SLOT;
+    uint8_t* dst = slots + (uint64_t)c * slot_stride;
     if (lane == 0) {
         dst[0] = (uint8_t)len; dst[1] = (uint8_t)(len >> 8);
         dst[2] = (uint8_t)(len >> 16); dst[3] = (uint8_t)(len >> 24);
@@ -487,7 +494,11 @@ __global__ void __launch_bounds__(WAVE) k_lz4_decompress_wave(const ChunkDesc* c
                                                               int verify_crc,
                                                               unsigned long long* error,
                                                               const uint32_t* crc_table,
-                                                              uint8_t* bad_chunks = nullptr) {
+                                                              uint8_t* bad_chunks = nullptr,
+                                                              uint32_t max_comp = LZ4_SLOT) {
+    // max_comp: lz4_max_comp(chunk length of THIS input) — a frame longer
+    // than that cannot be a valid chunk (corrupt offset table) and is never
+    // walked.
     // compressed bytes are read through L1/L2 (all-lane same-address reads
     // broadcast; no LDS staging -> higher occupancy, same trade as the
     // compressor's global-src variant). crc_table is the 8x256 sliced set.
@@ -502,7 +513,7 @@ __global__ void __launch_bounds__(WAVE) k_lz4_decompress_wave(const ChunkDesc* c
         uint32_t ci = (blockIdx.x - DB) * WAVE + (uint32_t)threadIdx.x;
         if (ci >= n) return;
         ChunkDesc ch = chunks[ci];
-        if (ch.comp_len > LZ4_SLOT) return;  // decode block flags it
+        if (ch.comp_len > max_comp) return;  // decode block flags it
         const uint8_t* s_comp = ch.comp;
         uint32_t crc = 0xFFFFFFFFu;
         uint32_t i = 0;
@@ -525,7 +536,7 @@ __global__ void __launch_bounds__(WAVE) k_lz4_decompress_wave(const ChunkDesc* c
     }
     if (c >= n) return;  // odd tail: second half-wave has no chunk
     ChunkDesc ch = chunks[c];
-    if (ch.comp_len > LZ4_SLOT) { if (lane == 0) { if (bad_chunks) bad_chunks[c] = 1; else atomicExch(error, 9ull); } return; }
+    if (ch.comp_len > max_comp) { if (lane == 0) { if (bad_chunks) bad_chunks[c] = 1; else atomicExch(error, 9ull); } return; }
     const uint8_t* s_comp = ch.comp;
     uint32_t hdr = s_comp[0] | (s_comp[1] << 8) | (s_comp[2] << 16) | ((uint32_t)s_comp[3] << 24);
     if (hdr != ch.out_len) { if (lane == 0) { if (bad_chunks) bad_chunks[c] = 1; else atomicExch(error, 2ull); } return; }

@@ -7,8 +7,10 @@
 // marker / predecessor / restore+commit machinery as the LZ4 kernel
 // (lz4_wave.h); probe positions come from the skip-heuristic offset table
 // (skip=32; inc=skip>>5) passed as a kernel argument.
-// Control flow mirrors tests/native/snappy_sim.h, which is proven byte-equal
-// to the model on CPU.
+// Control flow mirrors tests/native/snappy_sim.h (16 KiB chunks) and
+// tests/native/snappy_wave_mirror.h (register duplicate groups and the
+// bounded offset-table lookup, up to 64 KiB), both proven byte-equal to the
+// model on CPU.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "snappy_model.h"
@@ -306,7 +308,7 @@ __global__ void __launch_bounds__(WAVE) k_snappy_decompress_wave(const SnpChunk*
                 if (ip + 2 > iend) { fail(23); return; }
                 offset = in[ip] | ((uint32_t)in[ip + 1] << 8);
                 ip += 2;
-            } else {                        // 4-byte offset (never emitted for 16K chunks)
+            } else {                        // 4-byte offset (never emitted for <= 64 KiB chunks)
                 len = (tag >> 2) + 1;
                 if (ip + 4 > iend) { fail(23); return; }
                 memcpy(&offset, in + ip, 4);
@@ -344,19 +346,22 @@ __global__ void __launch_bounds__(WAVE) k_snappy_decompress_wave(const SnpChunk*
 
 // ---------------------------------------------------------------------------
 // product-pipeline kernels: same slot/csize/ccrc contract as the LZ4 pair in
-// lz4_wave.h (slot stride SNP_SLOT; payload = varint + fragment, CRC32 over
+// lz4_wave.h (slot stride snp_slot_stride(chunk_len); payload = varint + fragment, CRC32 over
 // the payload; CompressedSequentialWriter framing is codec-agnostic)
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(WAVE) k_snappy_compress_chunks(
     const uint8_t* data, uint64_t data_len, uint8_t* slots, uint32_t* csize, uint32_t* ccrc,
-    uint32_t n_chunks, const uint32_t* crc_table, const uint32_t* OFF, uint32_t off_n) {
+    uint32_t n_chunks, const uint32_t* crc_table, const uint32_t* OFF, uint32_t off_n,
+    uint32_t chunk_len = CHUNK_LEN, uint32_t slot_stride = SNP_SLOT) {
+    // chunk_len <= 64 KiB == one snappy fragment; the table is
+    // snp_table_size(len) <= SNP_MAX_TABLE entries at every supported length
     __shared__ uint16_t s_table[SNP_MAX_TABLE];
     uint32_t c = blockIdx.x;
     if (c >= n_chunks) return;
     int lane = threadIdx.x;
-    uint64_t off = (uint64_t)c * CHUNK_LEN;
-    uint32_t len = (uint32_t)min((uint64_t)CHUNK_LEN, data_len - off);
-    uint8_t* dst = slots + (uint64_t)c * SNP_SLOT;
+    uint64_t off = (uint64_t)c * chunk_len;
+    uint32_t len = (uint32_t)min((uint64_t)chunk_len, data_len - off);
+    uint8_t* dst = slots + (uint64_t)c * slot_stride;
     int csz = snp_wave_compress(data + off, len, dst, s_table, snp_table_size(len), OFF, off_n,
                                 lane);
     if (lane == 0) {
@@ -386,7 +391,8 @@ __global__ void __launch_bounds__(WAVE) k_snappy_decompress_chunks(const ChunkDe
                                                                    uint32_t n, int verify_crc,
                                                                    unsigned long long* error,
                                                                    const uint32_t* crc_table,
-                                                                   uint8_t* bad_chunks = nullptr) {
+                                                                   uint8_t* bad_chunks = nullptr,
+                                                                   uint32_t max_comp = SNP_SLOT) {
     // grid shared with the LZ4 decoder (lz4_decomp_grid): TWO chunks per
     // wave (one per half-wave — overlaps the serial tag-chain latencies),
     // CRC verification in trailing one-chunk-per-LANE blocks
@@ -398,7 +404,7 @@ __global__ void __launch_bounds__(WAVE) k_snappy_decompress_chunks(const ChunkDe
         uint32_t ci = (blockIdx.x - DB) * WAVE + (uint32_t)threadIdx.x;
         if (ci >= n) return;
         ChunkDesc ch = chunks[ci];
-        if (ch.comp_len > SNP_SLOT) return;  // decode block flags it
+        if (ch.comp_len > max_comp) return;  // decode block flags it
         const uint8_t* s_comp = ch.comp;
         uint32_t crc = 0xFFFFFFFFu;
         uint32_t i = 0;
@@ -423,7 +429,7 @@ __global__ void __launch_bounds__(WAVE) k_snappy_decompress_chunks(const ChunkDe
     (void)verify_crc;
     if (c >= n) return;  // odd tail half-wave
     ChunkDesc ch = chunks[c];
-    if (ch.comp_len > SNP_SLOT) { if (lane == 0) { if (bad_chunks) bad_chunks[c] = 1; else atomicExch(error, 9ull); } return; }
+    if (ch.comp_len > max_comp) { if (lane == 0) { if (bad_chunks) bad_chunks[c] = 1; else atomicExch(error, 9ull); } return; }
     const uint8_t* in = ch.comp;
     uint8_t* out = ch.out;
     uint32_t ip = 0, iend = ch.comp_len, olen = ch.out_len;

@@ -7,8 +7,13 @@
  * tables (big-format `oa`, Murmur3Partitioner, any partition key, up to 32
  * clustering columns of fixed (bigint/int) or variable (text/ascii/blob)
  * width including prefix range-tombstone bounds, 1..63 regular and 1..63
- * static columns with cell subsets, LZ4 chunk compression; row, cell,
- * partition and range tombstones all supported). The Java host above the seam
+ * static columns with cell subsets, LZ4 or Snappy chunk compression with any
+ * power-of-two chunk_length_in_kb from 1 to 64 KiB — inputs of one job may
+ * mix lengths; row, cell, partition and range tombstones all supported).
+ * Chunk lengths above 64 KiB are GPUC_ERR_UNSUPPORTED (liblz4 leaves its
+ * byU16 table at 65547 input bytes and snappy splits into several 64 KiB
+ * fragments: different algorithms); a zero or non-power-of-two length in a
+ * CompressionInfo.db is GPUC_ERR_FORMAT. The Java host above the seam
  * (strategies, CompactionManager, LifecycleTransaction, metrics) is
  * unchanged and binds these entry points via JNI/Panama.
  *
@@ -119,6 +124,14 @@ typedef struct gpuc_job {
        discards them exactly as it discards tmp files of an interrupted Java
        compaction (LifecycleTransaction abort). */
     const volatile int32_t* cancel_flag;
+
+    /* chunk length of the output sstable(s) in BYTES (the table's current
+       CompressionParams.chunk_length, as CompactionTask would pass it):
+       a power of two, 1024..65536. 0 == the chunk length of input_bases[0]
+       (what a compaction does when the params are unchanged). Applies to
+       every shard of n_output_shards. Inputs may have any supported length,
+       each its own. */
+    uint32_t output_chunk_length;
 } gpuc_job;
 
 typedef struct gpuc_result {
@@ -182,6 +195,8 @@ typedef struct gpuc_gen_spec {
                                    set (Partitions.db/Rows.db, BtiFormat.md) */
     int32_t counter;            /* 1: one CounterColumnType column with
                                    synthetic CounterContexts (CounterContext.java) */
+    uint32_t chunk_length;      /* output chunk length in bytes, power of two
+                                   1024..65536; 0 == 16 KiB */
 } gpuc_gen_spec;
 
 int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* error, size_t error_len);
@@ -202,7 +217,7 @@ int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partiti
  * Schema: `pk blob PRIMARY KEY, val blob`. values[i] == NULL makes row i a
  * row tombstone with local deletion time del_ldts[i] (else del_ldts ignored;
  * pass UINT32_MAX). Replaces the flush serialize/compress path of
- * Memtable.FlushablePartitionSet -> BigTableWriter. */
+ * Memtable.FlushablePartitionSet -> BigTableWriter. Always 16 KiB chunks. */
 typedef struct gpuc_flush_rows {
     uint64_t n_rows;
     const uint8_t* const* keys;
@@ -323,6 +338,8 @@ typedef struct gpuc_flush_schema {
     int64_t stats_min_ts;
     int64_t stats_min_ldt;      /* long-seconds semantics */
     int32_t stats_min_ttl;
+    uint32_t chunk_length;      /* output chunk length in bytes, power of two
+                                 * 1024..65536; 0 == 16 KiB */
 } gpuc_flush_schema;
 
 int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flush_part* parts,
@@ -330,9 +347,10 @@ int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flush_part* par
                      char* error, size_t error_len);
 
 /* Scrub one sstable (SortedTableScrubber): salvage every partition whose
- * byte range touches only CRC/decode-clean 16 KiB chunks and rewrite them as
- * a clean sstable under output_base (recovery granularity documented in
- * DESIGN.md; identical to the oracle's). kept/dropped may be NULL. */
+ * byte range touches only CRC/decode-clean chunks and rewrite them as a clean
+ * sstable under output_base, written at the INPUT's chunk length (recovery
+ * granularity is the chunk — documented in DESIGN.md; identical to the
+ * oracle's). kept/dropped may be NULL. */
 int gpuc_scrub(const char* input_base, const char* output_base, int32_t device,
                uint64_t* kept, uint64_t* dropped, char* error, size_t error_len);
 
@@ -342,6 +360,15 @@ int gpuc_scrub(const char* input_base, const char* output_base, int32_t device,
  * rebuild compared against Filter.db. GPUC_OK or GPUC_ERR_FORMAT with a
  * message. */
 int gpuc_verify(const char* input_base, int32_t device, char* error, size_t error_len);
+
+/* Diagnostic: chunk-compress a host buffer exactly as the writer does (the
+ * same kernel launches, not a copy) and return the Data.db image (per chunk:
+ * payload, then BE CRC32) plus the CompressionInfo.db chunk offsets.
+ * chunk_length: power of two 1024..65536 (0 == 16 KiB). */
+int gpuc_compress_buffer(const uint8_t* data, uint64_t len, uint32_t chunk_length,
+                         int32_t snappy, int32_t device, uint8_t* out, uint64_t out_cap,
+                         uint64_t* out_len, uint64_t* offsets, uint32_t offsets_cap,
+                         uint32_t* n_chunks, char* error, size_t error_len);
 
 /* library/build identification */
 const char* gpuc_version(void);

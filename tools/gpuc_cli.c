@@ -2,12 +2,15 @@
  * drop-in boundary (include/gpucompact.h) without C++ or Python. The Java
  * side would bind the same symbols via Panama FFI.
  *
- *   gpuc_cli compact <out_base> <in_base> [<in_base> ...]
+ *   gpuc_cli compact <out_base> [chunk=<bytes>] <in_base> [<in_base> ...]
+ *       chunk=: output chunk length (power of two, 1024..65536); default is
+ *       the chunk length of the first input
  *   gpuc_cli verify  <base>
  *   gpuc_cli scrub   <out_base> <in_base>
  */
 #include <stdio.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include "../include/gpucompact.h"
 
@@ -32,9 +35,15 @@ int main(int argc, char** argv) {
     }
     if (!strcmp(argv[1], "compact")) {
         const char* ins[64];
-        int k = argc - 3;
+        int first = 3;
+        uint32_t out_chunk = 0;
+        if (argc > 3 && !strncmp(argv[3], "chunk=", 6)) {
+            out_chunk = (uint32_t)strtoul(argv[3] + 6, NULL, 10);
+            first = 4;
+        }
+        int k = argc - first;
         if (k < 1 || k > 64) { fprintf(stderr, "1..64 inputs\n"); return 2; }
-        for (int i = 0; i < k; i++) ins[i] = argv[3 + i];
+        for (int i = 0; i < k; i++) ins[i] = argv[first + i];
         gpuc_job job;
         memset(&job, 0, sizeof job);
         job.input_bases = ins;
@@ -42,6 +51,7 @@ int main(int argc, char** argv) {
         job.output_base = argv[2];
         job.gc_before = INT64_MIN;
         job.never_purge = 1;
+        job.output_chunk_length = out_chunk;
         gpuc_result res;
         memset(&res, 0, sizeof res);
         int rc = gpuc_compact(&job, &res);
