@@ -21,8 +21,21 @@ constexpr uint32_t LDT_NONE_U32 = 0xFFFFFFFFu;
 constexpr int64_t TIMESTAMP_EPOCH = 1442880000000000LL;
 constexpr int64_t DELETION_TIME_EPOCH = 1442880000LL;
 // CompressionParams.DEFAULT_CHUNK_LENGTH: the default only — each sstable
-// carries its own chunk length (1..64 KiB, gpu_structs.h) as a runtime value
+// carries its own chunk length (1..64 KiB, below) as a runtime value
 constexpr uint32_t CHUNK_LEN = 16384;
+// Chunk lengths the codecs support: powers of two from 1 KiB to 64 KiB.
+// Above 64 KiB liblz4 leaves the byU16 table (at 65547 input bytes) and snappy
+// splits the input into several 64 KiB fragments — different algorithms.
+constexpr uint32_t MIN_CHUNK_LEN = 1024;
+constexpr uint32_t MAX_CHUNK_LEN = 65536;
+GPUC_HD constexpr bool chunk_len_pow2(uint32_t len) { return len && !(len & (len - 1)); }
+GPUC_HD constexpr bool chunk_len_supported(uint32_t len) {
+    return chunk_len_pow2(len) && len >= MIN_CHUNK_LEN && len <= MAX_CHUNK_LEN;
+}
+// largest valid chunk payload: 4-byte LE length + LZ4_compressBound(len) /
+// snappy_max_compressed_length(len). The decoders refuse longer frames.
+GPUC_HD constexpr uint32_t lz4_max_comp(uint32_t len) { return 4 + len + len / 255 + 16; }
+GPUC_HD constexpr uint32_t snp_max_comp(uint32_t len) { return 32 + len + len / 6; }
 
 GPUC_HD inline int64_t ldt_long(uint32_t u) { return u == LDT_NONE_U32 ? NO_DELETION_TIME : (int64_t)u; }
 GPUC_HD inline uint32_t ldt_u32(int64_t l) { return l == NO_DELETION_TIME ? LDT_NONE_U32 : (uint32_t)l; }

@@ -201,20 +201,7 @@ struct OutStats {
     unsigned long long cpx_alloc;                    // output cpx-cell arena bump
 };
 
-// Chunk lengths the codecs support: powers of two from 1 KiB to 64 KiB.
-// Above 64 KiB liblz4 leaves the byU16 table (at 65547 input bytes) and snappy
-// splits the input into several 64 KiB fragments — different algorithms.
-constexpr uint32_t MIN_CHUNK_LEN = 1024;
-constexpr uint32_t MAX_CHUNK_LEN = 65536;
-GPUC_HD constexpr bool chunk_len_pow2(uint32_t len) { return len && !(len & (len - 1)); }
-GPUC_HD constexpr bool chunk_len_supported(uint32_t len) {
-    return chunk_len_pow2(len) && len >= MIN_CHUNK_LEN && len <= MAX_CHUNK_LEN;
-}
-// largest valid chunk payload: 4-byte LE length + LZ4_compressBound(len) /
-// snappy_max_compressed_length(len). The decoders refuse longer frames.
-GPUC_HD constexpr uint32_t lz4_max_comp(uint32_t len) { return 4 + len + len / 255 + 16; }
-GPUC_HD constexpr uint32_t snp_max_comp(uint32_t len) { return 32 + len + len / 6; }
-// compressor output slot strides (16 B / 512 B aligned)
+// compressor output slot strides (16 B / 512 B aligned; bounds in codec.h)
 GPUC_HD constexpr uint32_t lz4_slot_stride(uint32_t len) { return (lz4_max_comp(len) + 15u) & ~15u; }
 GPUC_HD constexpr uint32_t snp_slot_stride(uint32_t len) { return (snp_max_comp(len) + 511u) & ~511u; }
 constexpr uint32_t LZ4_SLOT = lz4_slot_stride(CHUNK_LEN);  // 16480

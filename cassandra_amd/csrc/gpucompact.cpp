@@ -8,6 +8,7 @@
 #include "kernels.hip"
 #include "kernels_rows.hip"
 #include "bti_core.h"
+#include "sstable_meta.h"
 #include "../../include/gpucompact.h"
 
 #include <algorithm>
@@ -29,8 +30,6 @@
 
 namespace gpuc {
 
-using bytes = std::vector<uint8_t>;
-
 #define HIP_CHECK(x)                                                              \
     do {                                                                          \
         hipError_t _e = (x);                                                      \
@@ -50,27 +49,6 @@ static void put_uvint(bytes& o, uint64_t v) {
     int n = uvint_put(tmp, v);
     o.insert(o.end(), tmp, tmp + n);
 }
-
-struct HReader {
-    const uint8_t* p;
-    size_t len, pos = 0;
-    explicit HReader(const bytes& b) : p(b.data()), len(b.size()) {}
-    void need(size_t n) const { if (pos + n > len) throw std::runtime_error("short read in component"); }
-    uint8_t u8() { need(1); return p[pos++]; }
-    uint16_t be16() { need(2); uint16_t v = ((uint16_t)p[pos] << 8) | p[pos + 1]; pos += 2; return v; }
-    uint32_t be32() { need(4); uint32_t v = 0; for (int i = 0; i < 4; i++) v = (v << 8) | p[pos + i]; pos += 4; return v; }
-    uint64_t be64() { need(8); uint64_t v = 0; for (int i = 0; i < 8; i++) v = (v << 8) | p[pos + i]; pos += 8; return v; }
-    bytes take(size_t n) { need(n); bytes b(p + pos, p + pos + n); pos += n; return b; }
-    void skip(size_t n) { need(n); pos += n; }
-    uint64_t uvint() {
-        need(1);
-        uint64_t q = pos;
-        uint64_t v = uvint_get(p, &q);
-        if (q > len) throw std::runtime_error("vint overrun");
-        pos = q;
-        return v;
-    }
-};
 
 // grow-only pinned staging buffers, reused across calls (hipHostMalloc is
 // expensive; a compaction service reuses its staging arenas the same way)
@@ -183,157 +161,6 @@ static void write_file(const std::string& path, const uint8_t* p, size_t n) {
     if (!f) throw std::runtime_error("cannot create " + path);
     if (n && fwrite(p, 1, n, f) != n) { fclose(f); throw std::runtime_error("short write " + path); }
     fclose(f);
-}
-
-// ---------------------------------------------------------------------------
-// component parsing (input side)
-// ---------------------------------------------------------------------------
-// typed failures the C ABI maps to GPUC_ERR_UNSUPPORTED / GPUC_ERR_FORMAT
-struct unsupported_error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-struct format_error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
-static const char* const CHUNK_LEN_WHY =
-    " (supported: powers of two from 1 KiB to 64 KiB; above 64 KiB liblz4 leaves its byU16 "
-    "table and snappy splits into several 64 KiB fragments)";
-// a chunk length handed in as an ARGUMENT (0 == caller's default)
-static uint32_t checked_chunk_len_arg(uint32_t len, uint32_t dflt) {
-    if (len == 0) return dflt;
-    if (!chunk_len_supported(len))
-        throw unsupported_error("unsupported chunk_length " + std::to_string(len) + CHUNK_LEN_WHY);
-    return len;
-}
-
-struct HCompressionInfo {
-    uint32_t chunk_len = 16384;
-    uint32_t max_compressed = 0x7FFFFFFF;
-    uint64_t data_len = 0;
-    bool snappy = false;  // SnappyCompressor (else LZ4Compressor)
-    std::vector<uint64_t> offsets;
-    // decoder sanity bound for this input's frames (gpu_structs.h)
-    uint32_t max_comp() const { return snappy ? snp_max_comp(chunk_len) : lz4_max_comp(chunk_len); }
-};
-static HCompressionInfo parse_compression_info(const bytes& b) {
-    HReader r(b);
-    uint16_t nlen = r.be16();
-    bytes name = r.take(nlen);
-    std::string algo((char*)name.data(), name.size());
-    if (algo != "LZ4Compressor" && algo != "SnappyCompressor")
-        throw std::runtime_error("unsupported compressor " + algo + " (GPU path: LZ4/Snappy)");
-    uint32_t opts = r.be32();
-    for (uint32_t i = 0; i < opts; i++) { r.take(r.be16()); r.take(r.be16()); }
-    HCompressionInfo ci;
-    ci.snappy = algo == "SnappyCompressor";
-    ci.chunk_len = r.be32();
-    ci.max_compressed = r.be32();
-    ci.data_len = r.be64();
-    uint32_t n = r.be32();
-    // checked before the offset table is even read: nothing downstream (and
-    // no kernel) ever sees a length the codecs were not built for
-    if (!chunk_len_pow2(ci.chunk_len))
-        throw format_error("CompressionInfo.db: chunk_length " + std::to_string(ci.chunk_len) +
-                           " is not a power of two");
-    if (!chunk_len_supported(ci.chunk_len))
-        throw unsupported_error("unsupported chunk_length " + std::to_string(ci.chunk_len) +
-                                CHUNK_LEN_WHY);
-    ci.offsets.resize(n);
-    for (uint32_t i = 0; i < n; i++) ci.offsets[i] = r.be64();
-    return ci;
-}
-
-struct HStatistics {
-    // HEADER component
-    int64_t hdr_min_ts = TIMESTAMP_EPOCH;
-    int64_t hdr_min_ldt = DELETION_TIME_EPOCH;
-    int32_t hdr_min_ttl = 0;
-    std::string key_type;
-    std::vector<std::string> clustering_types;
-    std::vector<std::pair<bytes, std::string>> static_cols, regular_cols;
-    // STATS mins (for SerializationHeader.make of the output)
-    int64_t min_timestamp = 0, max_timestamp = 0;
-    int64_t min_ldt = NO_DELETION_TIME, max_ldt = 0;
-    int32_t min_ttl = 0, max_ttl = 0;
-    std::string partitioner;
-};
-static HStatistics parse_statistics(const bytes& b) {
-    HReader r(b);
-    uint32_t count = r.be32();
-    r.be32();
-    std::map<uint32_t, uint32_t> toc;
-    for (uint32_t i = 0; i < count; i++) {
-        uint32_t t = r.be32();
-        uint32_t pos = r.be32();
-        toc[t] = pos;
-    }
-    r.be32();
-    HStatistics st;
-    if (toc.count(0)) {
-        HReader v(b);
-        v.pos = toc[0];
-        uint16_t n = v.be16();
-        bytes s = v.take(n);
-        st.partitioner.assign((char*)s.data(), s.size());
-    }
-    if (!toc.count(3)) throw std::runtime_error("Statistics.db missing HEADER component");
-    {
-        HReader h(b);
-        h.pos = toc[3];
-        st.hdr_min_ts = (int64_t)h.uvint() + TIMESTAMP_EPOCH;
-        st.hdr_min_ldt = (int64_t)(int32_t)(uint32_t)h.uvint() + DELETION_TIME_EPOCH;
-        st.hdr_min_ttl = (int32_t)(uint32_t)h.uvint();
-        auto rstr = [&]() { size_t n = (size_t)h.uvint(); bytes s = h.take(n); return std::string((char*)s.data(), s.size()); };
-        st.key_type = rstr();
-        size_t nct = (size_t)h.uvint();
-        for (size_t i = 0; i < nct; i++) st.clustering_types.push_back(rstr());
-        for (auto* cols : {&st.static_cols, &st.regular_cols}) {
-            size_t nc = (size_t)h.uvint();
-            for (size_t i = 0; i < nc; i++) {
-                size_t nn = (size_t)h.uvint();
-                bytes name = h.take(nn);
-                cols->push_back({name, rstr()});
-            }
-        }
-    }
-    if (toc.count(2)) {
-        HReader s(b);
-        s.pos = toc[2];
-        for (int hh = 0; hh < 2; hh++) { uint32_t n = s.be32(); s.skip((size_t)n * 16); }
-        s.skip(12);
-        st.min_timestamp = (int64_t)s.be64();
-        st.max_timestamp = (int64_t)s.be64();
-        st.min_ldt = ldt_long(s.be32());
-        st.max_ldt = ldt_long(s.be32());
-        st.min_ttl = (int32_t)s.be32();
-        st.max_ttl = (int32_t)s.be32();
-    }
-    return st;
-}
-
-// Index.db -> partition positions (host thread; validates non-indexed entries)
-static void parse_index_positions(const bytes& ib, uint64_t data_len,
-                                  std::vector<uint64_t>& positions,
-                                  std::vector<uint64_t>* entry_offs, std::string& err) {
-    try {
-        HReader r(ib);
-        positions.reserve(ib.size() / 18 + 2);
-        if (entry_offs) entry_offs->reserve(ib.size() / 18 + 2);
-        while (r.pos < r.len) {
-            if (entry_offs) entry_offs->push_back(r.pos);
-            uint16_t klen = r.be16();
-            r.skip(klen);
-            uint64_t pos = r.uvint();
-            uint64_t promoted = r.uvint();
-            r.skip(promoted);
-            if (pos >= data_len || (!positions.empty() && pos <= positions.back()))
-                throw std::runtime_error("Index.db positions not increasing/in range");
-            positions.push_back(pos);
-        }
-        positions.push_back(data_len);
-    } catch (const std::exception& e) {
-        err = e.what();
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1036,6 +863,174 @@ static void launch_chunk_compress(bool snappy, const uint8_t* d_data, uint64_t d
                            (uint32_t*)nullptr, chunk_len, stride);
 }
 
+// ---------------------------------------------------------------------------
+// input front end shared by compact_one, gpuc_scrub and gpuc_verify:
+// chunk decode -> schema upload -> parse chain. Every helper issues on the
+// stream it is given and adds no synchronisation of its own (exscan_u64
+// inside the parse chain synchronises to read its total).
+// ---------------------------------------------------------------------------
+// Owning handles: destroyed on scope exit, error paths included. Declare a
+// Stream BEFORE the DevBufs used on it, so the buffers are released first.
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() { HIP_CHECK(hipStreamCreate(&s)); }
+    ~Stream() { (void)hipStreamDestroy(s); }
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() { HIP_CHECK(hipEventCreate(&e)); }
+    ~Event() { (void)hipEventDestroy(e); }
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    operator hipEvent_t() const { return e; }
+};
+
+// synchronise `stream`, then fetch the device error word; each caller maps
+// the code to its own message
+static unsigned long long read_dev_error(const DevBuf& d_error, hipStream_t stream) {
+    unsigned long long err = 0;
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(&err, d_error.p, 8, hipMemcpyDeviceToHost));
+    return err;
+}
+
+// validated frames -> decoder descriptors. d_comp holds the file's bytes
+// from offset comp_lo on; chunk i of the window decodes to d_out + i * chunk_len.
+static std::vector<ChunkDesc> chunk_descs(const std::vector<ChunkFrame>& frames,
+                                          const uint8_t* d_comp, uint64_t comp_lo,
+                                          uint8_t* d_out, uint32_t chunk_len) {
+    std::vector<ChunkDesc> chunks;
+    chunks.reserve(frames.size());
+    for (size_t i = 0; i < frames.size(); i++)
+        chunks.push_back({d_comp + (frames[i].off - comp_lo), d_out + i * (uint64_t)chunk_len,
+                          frames[i].comp_len, frames[i].out_len});
+    return chunks;
+}
+
+// The one place chunk-decompress kernels are launched. d_bad (scrub) takes a
+// per-chunk failure flag instead of failing the whole input.
+static void launch_chunk_decompress(const HCompressionInfo& ci, const DevBuf& d_chunks, size_t n,
+                                    const DevBuf& d_error, uint8_t* d_bad, hipStream_t stream) {
+    if (!n) return;
+    const dim3 grid(lz4_decomp_grid((uint32_t)n, 1));
+    if (ci.snappy)
+        hipLaunchKernelGGL(k_snappy_decompress_chunks, grid, dim3(WAVE), 0, stream,
+                           d_chunks.as<ChunkDesc>(), (uint32_t)n, 1,
+                           d_error.as<unsigned long long>(), (const uint32_t*)g_crc256, d_bad,
+                           ci.max_comp());
+    else
+        hipLaunchKernelGGL(k_lz4_decompress_wave, grid, dim3(WAVE), 0, stream,
+                           d_chunks.as<ChunkDesc>(), (uint32_t)n, 1,
+                           d_error.as<unsigned long long>(), (const uint32_t*)g_crc256, d_bad,
+                           ci.max_comp());
+}
+
+// whole-file ingest of scrub and verify: upload Data.db and decode every chunk.
+// The caller zeroes d_error (and d_bad) on `stream` first; `file` and this
+// object outlive the next synchronise of `stream`.
+struct DecodedFile {
+    DevBuf comp, data, chunks;
+    std::vector<ChunkDesc> h_chunks;
+    void issue(const HCompressionInfo& ci, const std::vector<ChunkFrame>& frames,
+               const bytes& file, const DevBuf& d_error, uint8_t* d_bad, hipStream_t stream) {
+        comp.alloc(file.size());
+        HIP_CHECK(hipMemcpyAsync(comp.p, file.data(), file.size(), hipMemcpyHostToDevice, stream));
+        data.alloc(ci.data_len + 16);
+        h_chunks = chunk_descs(frames, comp.as<uint8_t>(), 0, data.as<uint8_t>(), ci.chunk_len);
+        chunks.alloc(h_chunks.size() * sizeof(ChunkDesc) + 16);
+        HIP_CHECK(hipMemcpyAsync(chunks.p, h_chunks.data(), h_chunks.size() * sizeof(ChunkDesc),
+                                 hipMemcpyHostToDevice, stream));
+        launch_chunk_decompress(ci, chunks, h_chunks.size(), d_error, d_bad, stream);
+    }
+};
+
+// device copy of a HostSchema's width arrays
+struct DevSchema {
+    DevBuf ck_w, col_fixed, static_fixed;
+    // hs is read by async copies: it must outlive the next synchronise of `stream`
+    SchemaParams upload(const HostSchema& hs, hipStream_t stream) {
+        auto up = [&](DevBuf& d, const std::vector<int32_t>& h) {
+            d.alloc(h.size() * 4 + 8);
+            if (!h.empty())
+                HIP_CHECK(hipMemcpyAsync(d.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, stream));
+            return d.as<int32_t>();
+        };
+        SchemaParams sch{};
+        sch.n_ck = (uint32_t)hs.ck_widths.size();
+        sch.ck_w = up(ck_w, hs.ck_widths);
+        sch.n_cols = (uint32_t)hs.col_fixed.size();
+        sch.col_fixed = up(col_fixed, hs.col_fixed);
+        sch.n_cpx = hs.n_cpx;
+        sch.counters = hs.counters ? 1u : 0u;
+        sch.n_static = (uint32_t)hs.static_fixed.size();
+        sch.static_fixed = up(static_fixed, hs.static_fixed);
+        sch.column_index_size = 64 * 1024;
+        return sch;
+    }
+};
+
+// parsed input: per-partition columns, static rows, the unfiltered arena and
+// the complex-cell bases
+struct ParsedInput {
+    DevBuf pdm, pdl, rcnt, rbase, kaddr, cpxtot, cpxbase;
+    StaticColsBuf st;
+    UnfColsBuf rows;
+    ParsedCols pc{};
+    uint64_t total_rows = 0, total_cpx = 0;
+};
+// The parse chain for n_srcs sources over `total` partitions. Pass A
+// (k_parse_count) fills the merge records and partition columns; count_only
+// (verify) stops there and leaves pc.st empty. Then row counts are scanned
+// into row bases, the complex cells are counted and scanned when the schema
+// has a complex column, and pass B (k_parse_rows) decodes the rows.
+static void parse_input(ParsedInput& in, const DevBuf& d_srcs, uint32_t n_srcs, uint64_t total,
+                        const DevBuf& d_recs, const SchemaParams& sch, const DevBuf& d_error,
+                        const DevBuf& d_rows_in, bool count_only, hipStream_t stream) {
+    ParsedCols& pc = in.pc;
+    in.pdm.alloc(total * 8 + 8); pc.pdel_mfda = in.pdm.as<int64_t>();
+    in.pdl.alloc(total * 4 + 8); pc.pdel_ldt = in.pdl.as<uint32_t>();
+    in.rcnt.alloc(total * 4 + 8); pc.row_count = in.rcnt.as<uint32_t>();
+    in.rbase.alloc(total * 8 + 8); pc.row_base = in.rbase.as<uint64_t>();
+    in.kaddr.alloc(total * 8 + 8); pc.key_addr = in.kaddr.as<uint64_t>();
+    if (!count_only) {
+        in.st.alloc(sch.n_static ? total : 1, sch.n_static);
+        pc.st = in.st.st;
+    }
+    const dim3 grid((uint32_t)((total + 255) / 256)), block(256);
+    const SrcDesc2* srcs = d_srcs.as<SrcDesc2>();
+    unsigned long long* err = d_error.as<unsigned long long>();
+    if (total)
+        hipLaunchKernelGGL(k_parse_count, grid, block, 0, stream, srcs, n_srcs, (uint32_t)total,
+                           d_recs.as<MRec>(), pc, sch, err);
+    if (count_only) return;
+    if (total)
+        hipLaunchKernelGGL(k_widen_u32, grid, block, 0, stream, pc.row_count, pc.row_base, total);
+    in.total_rows = exscan_u64(pc.row_base, total, stream);
+    in.rows.alloc(in.total_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
+    if (!total) return;
+    auto rows_pass = [&](const uint64_t* cpx_bases) {
+        hipLaunchKernelGGL(k_parse_rows, grid, block, 0, stream, srcs, n_srcs, (uint32_t)total, pc,
+                           in.rows.uc, sch, err, d_rows_in.as<unsigned long long>(), cpx_bases);
+    };
+    if (sch.n_cpx) {
+        // counting pass: full walk, per-partition complex-cell totals, which
+        // size the cell arena and become each partition's base in it
+        in.cpxtot.alloc(total * 4 + 8);
+        pc.cpx_total = in.cpxtot.as<uint32_t>();
+        rows_pass(nullptr);
+        HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));  // recounted by the fill pass
+        in.cpxbase.alloc(total * 8 + 8);
+        hipLaunchKernelGGL(k_widen_u32, grid, block, 0, stream, pc.cpx_total,
+                           in.cpxbase.as<uint64_t>(), total);
+        in.total_cpx = exscan_u64(in.cpxbase.as<uint64_t>(), total, stream);
+        in.rows.alloc_cpx_arena(in.total_cpx);
+    }
+    rows_pass(sch.n_cpx ? in.cpxbase.as<uint64_t>() : nullptr);
+}
+
 static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfColsBuf& rows,
                                            uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
                                            DevBuf& d_tomb, uint32_t tomb_cap,
@@ -1062,9 +1057,9 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     HIP_CHECK(hipMemcpyAsync(d_ps_off.p, ps_off_h.data(), ps_off_h.size() * 8, hipMemcpyHostToDevice, stream));
     HIP_CHECK(hipMemcpyAsync(d_ch_off.p, ch_off_h.data(), ch_off_h.size() * 8, hipMemcpyHostToDevice, stream));
 
-    hipEvent_t ev0, ev1, ev2, ev3, ev4;
-    HIP_CHECK(hipEventCreate(&ev0)); HIP_CHECK(hipEventCreate(&ev1)); HIP_CHECK(hipEventCreate(&ev2));
-    HIP_CHECK(hipEventCreate(&ev3)); HIP_CHECK(hipEventCreate(&ev4));
+    // cstream drains finished output (below); declared ahead of the buffers it reads
+    Stream cstream;
+    Event ev0, ev1, ev2, ev3, ev4;
 
     // ---- collect stats (needed before bloom sizing) ----
     {
@@ -1124,8 +1119,6 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     // NEVER a third stream, and nothing ahead of the drain ops on cstream:
     // both alternatives measured -30% whole-step
     // (profiles/r02_drain_regression.md).
-    hipStream_t cstream;
-    HIP_CHECK(hipStreamCreate(&cstream));
     int NSEG = n_groups >= 4096 && total_unc > (256ull << 20) ? 8 : 1;
     if (const char* e = getenv("GPUC_NSEG")) NSEG = std::max(1, std::min(64, atoi(e)));
     if (n_groups < 4096) NSEG = 1;
@@ -1189,7 +1182,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         HIP_CHECK(hipMemcpyAsync(h_index, d_out_index.p, total_idx, hipMemcpyDeviceToHost, cstream));
     }
 
-    std::vector<hipEvent_t> ev_c(n_slabs);
+    std::vector<Event> ev_c(n_slabs);
     for (uint32_t i = 0; i < n_slabs; i++) {
         uint32_t cb = i * SLAB, m = std::min(SLAB, n_chunks - cb);
         if (NSEG > 1) {
@@ -1210,7 +1203,6 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
                               d_slots.as<uint8_t>() + (uint64_t)cb * SLOT_STRIDE,
                               d_csize.as<uint32_t>() + cb, d_ccrc.as<uint32_t>() + cb, m, OCL,
                               SLOT_STRIDE, stream);
-        HIP_CHECK(hipEventCreate(&ev_c[i]));
         HIP_CHECK(hipEventRecord(ev_c[i], stream));
     }
     if (NSEG > 1 && seg_issued <= NSEG) {
@@ -1563,9 +1555,6 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         w.ms_io = (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) / 1e6;
         w.ms_d2h = t_drain1 - t_drain0;  // slab drain wall (overlaps compress)
     }
-    for (uint32_t i = 0; i < n_slabs; i++) (void)hipEventDestroy(ev_c[i]);
-
-    HIP_CHECK(hipStreamDestroy(cstream));
     w.uncompressed_len = total_unc;
     float t01, t12, t23;
     HIP_CHECK(hipEventElapsedTime(&t01, ev0, ev1));
@@ -1574,7 +1563,6 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     w.ms_sizes = t01;
     w.ms_serialize = t12;
     w.ms_compress = t23;
-    for (auto e : {ev0, ev1, ev2, ev3, ev4}) (void)hipEventDestroy(e);
     return w;
 }
 
@@ -1598,17 +1586,6 @@ static void set_err(char* dst, size_t cap, const std::string& msg) {
     snprintf(dst, cap, "%s", msg.c_str());
 }
 
-// marshal type string -> clustering component width (-1 variable)
-static int32_t ck_type_width(const std::string& t) {
-    if (t == "org.apache.cassandra.db.marshal.LongType") return 8;
-    if (t == "org.apache.cassandra.db.marshal.Int32Type") return 4;
-    if (t == "org.apache.cassandra.db.marshal.UTF8Type" ||
-        t == "org.apache.cassandra.db.marshal.AsciiType" ||
-        t == "org.apache.cassandra.db.marshal.BytesType")
-        return -1;
-    throw std::runtime_error("unsupported clustering type " + t);
-}
-
 struct CompactSetup {
     int k = 0;        // total ingested sstables (data + tombstone sources)
     int k_data = 0;   // first k_data are the compacted data inputs
@@ -1622,12 +1599,8 @@ struct CompactSetup {
     std::vector<std::vector<uint64_t>> entry_offs;  // Index.db entry byte offsets
     std::vector<std::vector<bti::bytes>> bti_prefixes;  // da: trie separator per partition
     std::vector<size_t> comp_file_sz;
-    std::vector<int32_t> col_fixed_h;    // SIMPLE regular columns only
-    uint32_t n_cpx = 0;                  // one complex (map<blob,blob>) column, last
-    bool counters = false;               // counter table (every column CounterColumnType)
+    HostSchema schema;                   // resolved from stats[0]
     bool bti = false;                    // inputs are `da` (trie-indexed)
-    std::vector<int32_t> ck_widths;      // per clustering column
-    std::vector<int32_t> static_fixed_h; // per static column
     // unsharded fast path: whole-file Data.db reads started during index
     // parse as ordered STRIPES per source (compact_one adopts them when its
     // window covers the full file and overlaps H2D with the remaining reads)
@@ -1675,8 +1648,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
     };
     HIP_CHECK(hipSetDevice(job->device));
-    hipStream_t stream;
-    HIP_CHECK(hipStreamCreate(&stream));
+    Stream stream;
     {
         int k = su.k;
         const auto& in_bases = su.in_bases;
@@ -1684,33 +1656,21 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         const auto& stats = su.stats;
         const auto& generations = su.generations;
         const auto& positions = su.positions;
-        const auto& col_fixed_h = su.col_fixed_h;
 
         double t0 = wall();
         // per-input window: partition range -> chunk range -> compressed range
         std::vector<uint32_t> win_blo(k), win_n(k);
-        std::vector<uint64_t> win_chunk_lo(k), win_comp_lo(k);
+        std::vector<ChunkWindow> win(k);
+        std::vector<uint64_t> win_comp_lo(k);
         std::vector<size_t> comp_sz(k, 0);        // compressed bytes in window
         std::vector<uint8_t*> comp_pin(k, nullptr);
-        std::vector<uint64_t> data_lo(k), data_hi(k);  // uncompressed byte window
         for (int s = 0; s < k; s++) {
-            uint32_t blo = pr[s].first, bhi = pr[s].second;
-            win_blo[s] = blo;
-            win_n[s] = bhi - blo;
-            data_lo[s] = positions[s][blo];
-            data_hi[s] = positions[s][bhi];
-            const uint64_t icl = su.cinfos[s].chunk_len;  // per input
-            uint64_t c_lo = data_lo[s] / icl;
-            uint64_t c_hi = (data_hi[s] + icl - 1) / icl;
-            uint64_t n_chunks_file = su.cinfos[s].offsets.size();
-            if (c_hi > n_chunks_file) c_hi = n_chunks_file;
-            if (win_n[s] == 0) { c_lo = c_hi = 0; }
-            win_chunk_lo[s] = c_lo;
-            uint64_t comp_lo = c_lo < n_chunks_file ? cinfos[s].offsets[c_lo] : su.comp_file_sz[s];
-            uint64_t comp_hi = c_hi < n_chunks_file ? cinfos[s].offsets[c_hi] : su.comp_file_sz[s];
-            if (win_n[s] == 0) comp_lo = comp_hi = 0;
-            win_comp_lo[s] = comp_lo;
-            comp_sz[s] = comp_hi - comp_lo;
+            win_blo[s] = pr[s].first;
+            win_n[s] = pr[s].second - pr[s].first;
+            win[s] = chunk_window(cinfos[s], su.comp_file_sz[s], positions[s], pr[s].first,
+                                  pr[s].second);
+            win_comp_lo[s] = win[s].comp_lo;
+            comp_sz[s] = win[s].comp_hi - win[s].comp_lo;
         }
         bool adopt = !su.full_pin.empty();
         std::vector<std::thread> data_readers(adopt ? 0 : k);
@@ -1736,28 +1696,22 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         check_cancel(job);
 
         // ---- H2D + decompress (pipelined per sstable) ----
-        hipStream_t copy_stream;
-        HIP_CHECK(hipStreamCreate(&copy_stream));
-        hipEvent_t e0, e1, e2, e3, e4;
-        for (hipEvent_t* e : {&e0, &e1, &e2, &e3, &e4}) HIP_CHECK(hipEventCreate(e));
+        Stream copy_stream;
+        Event e0, e1, e2, e3, e4, er0, er1;
         HIP_CHECK(hipEventRecord(e0, stream));
         std::vector<DevBuf> d_comp(k), d_data(k), d_pos(k), d_chunks_s(k);
         DevBuf d_error;
         d_error.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_error.p, 0, 8, stream));
-        std::vector<hipEvent_t> ev_h2d(k);
+        std::vector<Event> ev_h2d(k);  // one per input: its uploads are done
         std::vector<std::vector<ChunkDesc>> chunks_all(k);  // kept alive past async copies
         double ms_read_data = 0;
         std::vector<const uint8_t*> vbase(k, nullptr);  // virtual decompressed origin
         for (int s = 0; s < k; s++) {
             double tr = wall();
             auto& ci = cinfos[s];
-            uint64_t n_chunks_file = ci.offsets.size();
-            uint64_t c_lo = win_chunk_lo[s];
             const uint64_t icl = ci.chunk_len;  // inputs of one job may differ
-            uint64_t c_hi = win_n[s] ? (data_hi[s] + icl - 1) / icl : c_lo;
-            if (c_hi > n_chunks_file) c_hi = n_chunks_file;
-            uint64_t n_wchunks = c_hi - c_lo;
+            const uint64_t c_lo = win[s].c_lo, n_wchunks = win[s].c_hi - c_lo;
             d_comp[s].alloc(comp_sz[s] ? comp_sz[s] : 1);
             if (adopt && win_comp_lo[s] == 0 && comp_sz[s] == su.comp_file_sz[s]) {
                 // stripe-progressive H2D: copy each stripe as its read lands
@@ -1795,37 +1749,16 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             HIP_CHECK(hipMemcpyAsync(d_pos[s].p, positions[s].data() + win_blo[s], n_wpos * 8,
                                      hipMemcpyHostToDevice, copy_stream));
             auto& chunks = chunks_all[s];
-            chunks.reserve(n_wchunks);
-            for (uint64_t c = c_lo; c < c_hi; c++) {
-                uint64_t off = ci.offsets[c];
-                uint64_t end = c + 1 < n_chunks_file ? ci.offsets[c + 1] : su.comp_file_sz[s];
-                ChunkDesc cd;
-                cd.comp = d_comp[s].as<uint8_t>() + (off - win_comp_lo[s]);
-                cd.out = d_data[s].as<uint8_t>() + (c - c_lo) * icl;
-                cd.comp_len = (uint32_t)(end - off - 4);
-                cd.out_len = (uint32_t)std::min<uint64_t>(icl, ci.data_len - c * icl);
-                chunks.push_back(cd);
-            }
+            chunks = chunk_descs(chunk_frames(ci, su.comp_file_sz[s], c_lo, win[s].c_hi),
+                                 d_comp[s].as<uint8_t>(), win_comp_lo[s],
+                                 d_data[s].as<uint8_t>(), ci.chunk_len);
             d_chunks_s[s].alloc(chunks.size() * sizeof(ChunkDesc) + 16);
             if (!chunks.empty())
                 HIP_CHECK(hipMemcpyAsync(d_chunks_s[s].p, chunks.data(), chunks.size() * sizeof(ChunkDesc),
                                          hipMemcpyHostToDevice, copy_stream));
-            HIP_CHECK(hipEventCreate(&ev_h2d[s]));
             HIP_CHECK(hipEventRecord(ev_h2d[s], copy_stream));
             HIP_CHECK(hipStreamWaitEvent(stream, ev_h2d[s], 0));
-            if (!chunks.empty()) {
-                if (ci.snappy)
-                    hipLaunchKernelGGL(k_snappy_decompress_chunks,
-                                       dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
-                                       stream, d_chunks_s[s].as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                                       d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                       (uint8_t*)nullptr, ci.max_comp());
-                else
-                    hipLaunchKernelGGL(k_lz4_decompress_wave, dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
-                                       stream, d_chunks_s[s].as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                                       d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                       (uint8_t*)nullptr, ci.max_comp());
-            }
+            launch_chunk_decompress(ci, d_chunks_s[s], chunks.size(), d_error, nullptr, stream);
         }
         {
             std::lock_guard<std::mutex> g(res_mu);
@@ -1838,14 +1771,9 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         // corrupt inputs must fail cleanly, not fault the GPU: the parse
         // walk trusts decompressed bytes, so the chunk-CRC verdict is checked
         // BEFORE any parse kernel touches them
-        {
-            unsigned long long err = 0;
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(&err, d_error.p, 8, hipMemcpyDeviceToHost));
-            if (err)
-                throw std::runtime_error("input chunk decompress/CRC failed, code " +
-                                         std::to_string(err));
-        }
+        if (unsigned long long err = read_dev_error(d_error, stream))
+            throw std::runtime_error("input chunk decompress/CRC failed, code " +
+                                     std::to_string(err));
 
         // ---- parse (pass A: count + partition meta; pass B: row decode) ----
         uint64_t total_parts = 0;
@@ -1861,30 +1789,8 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             total_parts += srcs[s].n_parts;
         }
         if (total_parts > 0xFFFFFFFFull) throw std::runtime_error("too many partitions for one job");
-        SchemaParams sch{};
-        sch.n_ck = (uint32_t)su.ck_widths.size();
-        DevBuf d_ck_w;
-        d_ck_w.alloc(su.ck_widths.size() * 4 + 8);
-        if (sch.n_ck)
-            HIP_CHECK(hipMemcpyAsync(d_ck_w.p, su.ck_widths.data(), su.ck_widths.size() * 4,
-                                     hipMemcpyHostToDevice, stream));
-        sch.ck_w = d_ck_w.as<int32_t>();
-        sch.n_cols = (uint32_t)col_fixed_h.size();
-        sch.n_cpx = su.n_cpx;
-        sch.counters = su.counters ? 1u : 0u;
-        DevBuf d_col_fixed;
-        d_col_fixed.alloc(col_fixed_h.size() * 4);
-        HIP_CHECK(hipMemcpyAsync(d_col_fixed.p, col_fixed_h.data(), col_fixed_h.size() * 4,
-                                 hipMemcpyHostToDevice, stream));
-        sch.col_fixed = d_col_fixed.as<int32_t>();
-        sch.n_static = (uint32_t)su.static_fixed_h.size();
-        DevBuf d_static_fixed;
-        d_static_fixed.alloc(su.static_fixed_h.size() * 4 + 8);
-        if (sch.n_static)
-            HIP_CHECK(hipMemcpyAsync(d_static_fixed.p, su.static_fixed_h.data(),
-                                     su.static_fixed_h.size() * 4, hipMemcpyHostToDevice, stream));
-        sch.static_fixed = d_static_fixed.as<int32_t>();
-        sch.column_index_size = 64 * 1024;
+        DevSchema dsch;
+        SchemaParams sch = dsch.upload(su.schema, stream);
         DevBuf d_srcs, d_recs_a, d_recs_b, d_rows_in;
         d_srcs.alloc(srcs.size() * sizeof(SrcDesc2));
         HIP_CHECK(hipMemcpyAsync(d_srcs.p, srcs.data(), srcs.size() * sizeof(SrcDesc2),
@@ -1893,60 +1799,17 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         d_recs_b.alloc(total_parts * sizeof(MRec));
         d_rows_in.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
-        DevBuf p_pdm, p_pdl, p_rcnt, p_rbase;
-        ParsedCols pc{};
-        p_pdm.alloc(total_parts * 8); pc.pdel_mfda = p_pdm.as<int64_t>();
-        p_pdl.alloc(total_parts * 4); pc.pdel_ldt = p_pdl.as<uint32_t>();
-        p_rcnt.alloc(total_parts * 4); pc.row_count = p_rcnt.as<uint32_t>();
-        p_rbase.alloc(total_parts * 8); pc.row_base = p_rbase.as<uint64_t>();
-        DevBuf p_kaddr;
-        p_kaddr.alloc(total_parts * 8); pc.key_addr = p_kaddr.as<uint64_t>();
-        StaticColsBuf p_static;
-        p_static.alloc(sch.n_static ? total_parts : 1, sch.n_static);
-        pc.st = p_static.st;
-        {
-            uint32_t blocks = (uint32_t)((total_parts + 255) / 256);
-            hipLaunchKernelGGL(k_parse_count, dim3(blocks), dim3(256), 0, stream,
-                               d_srcs.as<SrcDesc2>(), (uint32_t)k, (uint32_t)total_parts,
-                               d_recs_a.as<MRec>(), pc, sch, d_error.as<unsigned long long>());
-            hipLaunchKernelGGL(k_widen_u32, dim3(blocks), dim3(256), 0, stream,
-                               pc.row_count, pc.row_base, total_parts);
-        }
-        uint64_t total_in_rows = exscan_u64(pc.row_base, total_parts, stream);
-        UnfColsBuf in_rows;
-        in_rows.alloc(total_in_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
-        DevBuf p_cpxtot, p_cpxbase;
-        uint64_t total_in_cpx = 0;
-        {
-            uint32_t blocks = (uint32_t)((total_parts + 255) / 256);
-            if (sch.n_cpx) {
-                // pass B1 (COUNT): full walk, per-partition complex-cell totals
-                p_cpxtot.alloc(total_parts * 4 + 8);
-                pc.cpx_total = p_cpxtot.as<uint32_t>();
-                hipLaunchKernelGGL(k_parse_rows, dim3(blocks), dim3(256), 0, stream,
-                                   d_srcs.as<SrcDesc2>(), (uint32_t)k, (uint32_t)total_parts, pc,
-                                   in_rows.uc, sch, d_error.as<unsigned long long>(),
-                                   d_rows_in.as<unsigned long long>(), nullptr);
-                HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));  // recounted by pass B2
-                p_cpxbase.alloc(total_parts * 8 + 8);
-                hipLaunchKernelGGL(k_widen_u32, dim3(blocks), dim3(256), 0, stream,
-                                   pc.cpx_total, p_cpxbase.as<uint64_t>(), total_parts);
-                total_in_cpx = exscan_u64(p_cpxbase.as<uint64_t>(), total_parts, stream);
-                in_rows.alloc_cpx_arena(total_in_cpx);
-            }
-            hipLaunchKernelGGL(k_parse_rows, dim3(blocks), dim3(256), 0, stream,
-                               d_srcs.as<SrcDesc2>(), (uint32_t)k, (uint32_t)total_parts, pc,
-                               in_rows.uc, sch, d_error.as<unsigned long long>(),
-                               d_rows_in.as<unsigned long long>(),
-                               sch.n_cpx ? p_cpxbase.as<uint64_t>() : nullptr);
-        }
+        ParsedInput parsed;
+        parse_input(parsed, d_srcs, (uint32_t)k, total_parts, d_recs_a, sch, d_error, d_rows_in,
+                    false, stream);
+        const ParsedCols& pc = parsed.pc;
+        const UnfColsBuf& in_rows = parsed.rows;
+        const uint64_t total_in_rows = parsed.total_rows, total_in_cpx = parsed.total_cpx;
         HIP_CHECK(hipEventRecord(e3, stream));
         {
-            unsigned long long err = 0;
-            HIP_CHECK(hipStreamSynchronize(stream));
+            unsigned long long err = read_dev_error(d_error, stream);
             TR("parse synced");
-        check_cancel(job);
-            HIP_CHECK(hipMemcpy(&err, d_error.p, 8, hipMemcpyDeviceToHost));
+            check_cancel(job);  // a set cancel flag takes precedence over a parse error
             if (err) throw std::runtime_error("GPU decode/parse error code " + std::to_string(err));
             uint64_t rows_in_local = 0;
             HIP_CHECK(hipMemcpy(&rows_in_local, d_rows_in.p, 8, hipMemcpyDeviceToHost));
@@ -2150,9 +2013,6 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 pp.ov_has_bloom = 1;
             }
         }
-        hipEvent_t er0, er1;
-        HIP_CHECK(hipEventCreate(&er0));
-        HIP_CHECK(hipEventCreate(&er1));
         HIP_CHECK(hipEventRecord(er0, stream));
         // GC mode: purge is DEFERRED until after the garbage filter
         // (GarbageSkipper runs before the Purger in CompactionIterator)
@@ -2178,12 +2038,8 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         HIP_CHECK(hipEventRecord(er1, stream));
         HIP_CHECK(hipEventRecord(e4, stream));
         TR("reconcile issued");
-        HIP_CHECK(hipStreamSynchronize(stream));
-        {
-            unsigned long long err = 0;
-            HIP_CHECK(hipMemcpy(&err, d_error.p, 8, hipMemcpyDeviceToHost));
-            if (err) throw std::runtime_error("GPU reconcile error code " + std::to_string(err));
-        }
+        if (unsigned long long err = read_dev_error(d_error, stream))
+            throw std::runtime_error("GPU reconcile error code " + std::to_string(err));
 
         // ---- garbage collect: merge the tombstone sources, filter, purge ----
         UnfColsBuf gc_rows;          // filtered data arena (replaces out_rows)
@@ -2284,12 +2140,8 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 hipLaunchKernelGGL(k_purge_parts, dim3(blocks_g), dim3(256), 0, stream, opb.op,
                                    gc_rows.uc, n_groups, sch, pp, d_stats.as<OutStats>());
             }
-            HIP_CHECK(hipStreamSynchronize(stream));
-            {
-                unsigned long long err = 0;
-                HIP_CHECK(hipMemcpy(&err, d_error.p, 8, hipMemcpyDeviceToHost));
-                if (err) throw std::runtime_error("GPU gc filter error code " + std::to_string(err));
-            }
+            if (unsigned long long err = read_dev_error(d_error, stream))
+                throw std::runtime_error("GPU gc filter error code " + std::to_string(err));
             rows_for_writer = &gc_rows;
             TR("garbage filtered");
         }
@@ -2370,7 +2222,6 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 std::lock_guard<std::mutex> gl(res_mu);
                 res->partitions_out += cnt;
             }
-            HIP_CHECK(hipStreamDestroy(stream));
             return;
         }
         WriteDeviceOut w = write_sstable_device(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
@@ -2415,11 +2266,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 }
             res->dominant_kernel_launches = 1;
         }
-        for (hipEvent_t e : {e0, e1, e2, e3, e4, er0, er1}) (void)hipEventDestroy(e);
-        for (int s = 0; s < k; s++) (void)hipEventDestroy(ev_h2d[s]);
-        HIP_CHECK(hipStreamDestroy(copy_stream));
     }
-    HIP_CHECK(hipStreamDestroy(stream));
 }
 
 
@@ -2554,58 +2401,7 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
         size_t a = name.find('-'), b2 = name.find('-', a + 1);
         su.generations[s] = std::stoull(name.substr(a + 1, b2 - a - 1));
     }
-    {
-        const auto& rcols = su.stats[0].regular_cols;
-        for (size_t ci = 0; ci < rcols.size(); ci++) {
-            const std::string& ct = rcols[ci].second;
-            if (ct == "org.apache.cassandra.db.marshal.LongType") su.col_fixed_h.push_back(8);
-            else if (ct == "org.apache.cassandra.db.marshal.Int32Type") su.col_fixed_h.push_back(4);
-            else if (ct == "org.apache.cassandra.db.marshal.BytesType" ||
-                     ct == "org.apache.cassandra.db.marshal.UTF8Type" ||
-                     ct == "org.apache.cassandra.db.marshal.AsciiType")
-                su.col_fixed_h.push_back(-1);
-            else if (ct == "org.apache.cassandra.db.marshal.CounterColumnType") {
-                su.col_fixed_h.push_back(-1);
-                su.counters = true;
-            }
-            else if (ct == "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,org.apache.cassandra.db.marshal.BytesType)") {
-                // one complex column, and it must be the LAST regular column
-                // (engine layout constraint; the generator names it 'zm' so
-                // name order puts it last)
-                if (su.n_cpx || ci + 1 != rcols.size())
-                    throw std::runtime_error("at most one complex column, as the last regular column");
-                su.n_cpx = 1;
-            } else {
-                throw std::runtime_error("unsupported column type " + ct);
-            }
-        }
-        if (su.counters) {
-            // counter tables hold only counter columns (CreateTableStatement
-            // forbids mixing); complex/static columns are rejected with them
-            if (su.col_fixed_h.size() != rcols.size() || su.n_cpx)
-                throw std::runtime_error("counter tables must be all-counter columns");
-            for (auto& cp : rcols)
-                if (cp.second != "org.apache.cassandra.db.marshal.CounterColumnType")
-                    throw std::runtime_error("counter tables must be all-counter columns");
-            if (!su.stats[0].static_cols.empty())
-                throw std::runtime_error("static columns with counters unsupported");
-        }
-    }
-    for (auto& t : su.stats[0].clustering_types) su.ck_widths.push_back(ck_type_width(t));
-    for (auto& [nm2, ct2] : su.stats[0].static_cols) {
-        (void)nm2;
-        if (ct2 == "org.apache.cassandra.db.marshal.LongType") su.static_fixed_h.push_back(8);
-        else if (ct2 == "org.apache.cassandra.db.marshal.Int32Type") su.static_fixed_h.push_back(4);
-        else if (ct2 == "org.apache.cassandra.db.marshal.BytesType" ||
-                 ct2 == "org.apache.cassandra.db.marshal.UTF8Type" ||
-                 ct2 == "org.apache.cassandra.db.marshal.AsciiType")
-            su.static_fixed_h.push_back(-1);
-        else throw std::runtime_error("unsupported static column type " + ct2);
-    }
-    if (su.static_fixed_h.size() > 63)
-        throw std::runtime_error("1..63 static columns supported");
-    if (su.ck_widths.size() > 32)
-        throw std::runtime_error("at most 32 clustering columns supported");
+    su.schema = resolve_schema(su.stats[0]);
     if (su.bti) {
         // positions collected from the tries above; append the end sentinel
         for (int s = 0; s < k; s++) su.positions[s].push_back(su.cinfos[s].data_len);
@@ -2646,10 +2442,8 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
         if (ndev <= 0) { set_err(res->error, sizeof(res->error), "no HIP device (no CPU fallback)"); return GPUC_ERR_NO_GPU; }
         HIP_CHECK(hipSetDevice(job->device));
         {
-            hipStream_t s0;
-            HIP_CHECK(hipStreamCreate(&s0));
+            Stream s0;
             ensure_crc_tables(s0);
-            HIP_CHECK(hipStreamDestroy(s0));
         }
         if (job->n_inputs < 1 || job->n_inputs + (job->n_tomb_sources > 0 ? job->n_tomb_sources : 0) > 64) {
             set_err(res->error, sizeof(res->error), "n_inputs (+ tombstone sources) must be 1..64");
@@ -2824,20 +2618,19 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
     try {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         HIP_CHECK(hipSetDevice(device));
-        hipStream_t stream;
-        HIP_CHECK(hipStreamCreate(&stream));
+        Stream stream;
         ensure_crc_tables(stream);
         std::string base = input_base;
         bytes index_data = read_file(base + "-Index.db");
         HCompressionInfo ci = parse_compression_info(read_file(base + "-CompressionInfo.db"));
         HStatistics st = parse_statistics(read_file(base + "-Statistics.db"));
-        size_t comp_sz = file_size_of(base + "-Data.db");
         bytes comp = read_file(base + "-Data.db");
         std::vector<uint64_t> positions;
         std::string perr;
         parse_index_positions(index_data, ci.data_len, positions, nullptr, perr);
         if (!perr.empty()) throw std::runtime_error("Index.db: " + perr);
         uint64_t n_parts = positions.size() - 1;
+        const std::vector<ChunkFrame> frames = chunk_frames(ci, comp.size(), 0, ci.offsets.size());
 
         // digest from the chunk frames (CRC fields validated against bytes below)
         {
@@ -2845,10 +2638,9 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
             uint32_t tab[256];
             crc32_make_table(tab);
             uint32_t digest = 0;
-            for (size_t c = 0; c < ci.offsets.size(); c++) {
-                uint64_t off = ci.offsets[c];
-                uint64_t end = c + 1 < ci.offsets.size() ? ci.offsets[c + 1] : comp_sz;
-                uint64_t blen = end - off - 4;
+            for (const ChunkFrame& fr : frames) {
+                uint64_t blen = fr.comp_len;
+                uint64_t end = fr.off + blen + 4;
                 uint32_t ccrc = ((uint32_t)comp[end - 4] << 24) | ((uint32_t)comp[end - 3] << 16) |
                                 ((uint32_t)comp[end - 2] << 8) | comp[end - 1];
                 digest = comb.combine(digest, ccrc, blen);
@@ -2861,88 +2653,25 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         }
 
         // GPU: decompress (chunk CRC verify) + structural walk + order + bloom
-        DevBuf d_comp, d_data, d_pos, d_chunks, d_error, d_recs;
-        d_comp.alloc(comp.size());
-        HIP_CHECK(hipMemcpyAsync(d_comp.p, comp.data(), comp.size(), hipMemcpyHostToDevice, stream));
-        d_data.alloc(ci.data_len + 16);
+        DevBuf d_pos, d_error, d_recs;
         d_pos.alloc(positions.size() * 8);
         HIP_CHECK(hipMemcpyAsync(d_pos.p, positions.data(), positions.size() * 8,
                                  hipMemcpyHostToDevice, stream));
-        std::vector<ChunkDesc> chunks;
-        for (size_t c = 0; c < ci.offsets.size(); c++) {
-            uint64_t off = ci.offsets[c];
-            uint64_t end = c + 1 < ci.offsets.size() ? ci.offsets[c + 1] : comp_sz;
-            ChunkDesc cd;
-            cd.comp = d_comp.as<uint8_t>() + off;
-            cd.out = d_data.as<uint8_t>() + c * (uint64_t)ci.chunk_len;
-            cd.comp_len = (uint32_t)(end - off - 4);
-            cd.out_len = (uint32_t)std::min<uint64_t>(ci.chunk_len, ci.data_len - c * (uint64_t)ci.chunk_len);
-            chunks.push_back(cd);
-        }
-        d_chunks.alloc(chunks.size() * sizeof(ChunkDesc) + 16);
-        HIP_CHECK(hipMemcpyAsync(d_chunks.p, chunks.data(), chunks.size() * sizeof(ChunkDesc),
-                                 hipMemcpyHostToDevice, stream));
         d_error.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_error.p, 0, 8, stream));
-        if (!chunks.empty())
-            if (ci.snappy)
-                hipLaunchKernelGGL(k_snappy_decompress_chunks,
-                                   dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
-                                   stream, d_chunks.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                                   d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                   (uint8_t*)nullptr, ci.max_comp());
-            else
-                hipLaunchKernelGGL(k_lz4_decompress_wave, dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
-                               stream, d_chunks.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                               d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                               (uint8_t*)nullptr, ci.max_comp());
+        DecodedFile dec;
+        dec.issue(ci, frames, comp, d_error, nullptr, stream);
+        const DevBuf& d_data = dec.data;
         {
-            unsigned long long e = 0;
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(&e, d_error.p, 8, hipMemcpyDeviceToHost));
+            unsigned long long e = read_dev_error(d_error, stream);
             if (e == 1) throw std::runtime_error("chunk CRC mismatch");
             if (e) throw std::runtime_error("chunk decompress failed, code " + std::to_string(e));
         }
-        SchemaParams sch{};
-        std::vector<int32_t> cfh;
-        for (auto& [nm, ct] : st.regular_cols) {
-            (void)nm;
-            if (ct == "org.apache.cassandra.db.marshal.LongType") cfh.push_back(8);
-            else if (ct == "org.apache.cassandra.db.marshal.Int32Type") cfh.push_back(4);
-            else if (ct == "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,org.apache.cassandra.db.marshal.BytesType)") sch.n_cpx = 1;  // last regular column
-            else cfh.push_back(-1);
-        }
-        if (cfh.empty() && !sch.n_cpx) cfh.push_back(-1);
-        sch.n_cols = (uint32_t)cfh.size();
+        HostSchema hsch = resolve_schema(st);
+        if (hsch.col_fixed.empty() && !hsch.n_cpx) hsch.col_fixed.push_back(-1);
+        DevSchema dsch;
+        SchemaParams sch = dsch.upload(hsch, stream);
         if (!sch.n_cols && !sch.n_cpx) sch.n_cols = 1;
-        DevBuf d_cf;
-        d_cf.alloc(cfh.size() * 4);
-        HIP_CHECK(hipMemcpyAsync(d_cf.p, cfh.data(), cfh.size() * 4, hipMemcpyHostToDevice, stream));
-        sch.col_fixed = d_cf.as<int32_t>();
-        std::vector<int32_t> vckw;
-        for (auto& ct : st.clustering_types) vckw.push_back(ck_type_width(ct));
-        sch.n_ck = (uint32_t)vckw.size();
-        DevBuf d_vckw;
-        d_vckw.alloc(vckw.size() * 4 + 8);
-        if (sch.n_ck)
-            HIP_CHECK(hipMemcpyAsync(d_vckw.p, vckw.data(), vckw.size() * 4,
-                                     hipMemcpyHostToDevice, stream));
-        sch.ck_w = d_vckw.as<int32_t>();
-        std::vector<int32_t> vsf;
-        for (auto& [snm, sct] : st.static_cols) {
-            (void)snm;
-            if (sct == "org.apache.cassandra.db.marshal.LongType") vsf.push_back(8);
-            else if (sct == "org.apache.cassandra.db.marshal.Int32Type") vsf.push_back(4);
-            else vsf.push_back(-1);
-        }
-        sch.n_static = (uint32_t)vsf.size();
-        DevBuf d_vsf;
-        d_vsf.alloc(vsf.size() * 4 + 8);
-        if (sch.n_static)
-            HIP_CHECK(hipMemcpyAsync(d_vsf.p, vsf.data(), vsf.size() * 4,
-                                     hipMemcpyHostToDevice, stream));
-        sch.static_fixed = d_vsf.as<int32_t>();
-        sch.column_index_size = 64 * 1024;
         SrcDesc2 src{};
         src.data = d_data.as<uint8_t>();
         src.part_pos = d_pos.as<uint64_t>();
@@ -2955,18 +2684,12 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         d_src.alloc(sizeof(src));
         HIP_CHECK(hipMemcpyAsync(d_src.p, &src, sizeof(src), hipMemcpyHostToDevice, stream));
         d_recs.alloc((n_parts + 1) * sizeof(MRec));
-        DevBuf p_pdm, p_pdl, p_rcnt, p_rbase, p_kaddr;
-        ParsedCols pc{};
-        p_pdm.alloc(n_parts * 8 + 8); pc.pdel_mfda = p_pdm.as<int64_t>();
-        p_pdl.alloc(n_parts * 4 + 8); pc.pdel_ldt = p_pdl.as<uint32_t>();
-        p_rcnt.alloc(n_parts * 4 + 8); pc.row_count = p_rcnt.as<uint32_t>();
-        p_rbase.alloc(n_parts * 8 + 8); pc.row_base = p_rbase.as<uint64_t>();
-        p_kaddr.alloc(n_parts * 8 + 8); pc.key_addr = p_kaddr.as<uint64_t>();
+        // pass A only: it walks every row's structure; nothing here needs the rows
+        ParsedInput parsed;
+        parse_input(parsed, d_src, 1u, n_parts, d_recs, sch, d_error, DevBuf(), true, stream);
+        const ParsedCols& pc = parsed.pc;
         uint32_t blocks = (uint32_t)((n_parts + 255) / 256);
         if (n_parts) {
-            hipLaunchKernelGGL(k_parse_count, dim3(blocks), dim3(256), 0, stream,
-                               d_src.as<SrcDesc2>(), 1u, (uint32_t)n_parts, d_recs.as<MRec>(),
-                               pc, sch, d_error.as<unsigned long long>());
             KeyLut lut{};
             lut.base[0] = d_data.as<uint8_t>();
             lut.pos[0] = d_pos.as<uint64_t>();
@@ -2998,7 +2721,6 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
             if (memcmp(got.data(), f.data() + 8, std::min<size_t>(got.size(), f.size() - 8)) != 0)
                 throw std::runtime_error("Filter.db does not match keys");
         }
-        HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());
@@ -3018,14 +2740,12 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
     try {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         HIP_CHECK(hipSetDevice(device));
-        hipStream_t stream;
-        HIP_CHECK(hipStreamCreate(&stream));
+        Stream stream;
         ensure_crc_tables(stream);
         std::string base = input_base;
         bytes index_data = read_file(base + "-Index.db");
         HCompressionInfo ci = parse_compression_info(read_file(base + "-CompressionInfo.db"));
         HStatistics st = parse_statistics(read_file(base + "-Statistics.db"));
-        size_t comp_sz = file_size_of(base + "-Data.db");
         bytes comp = read_file(base + "-Data.db");
         std::vector<uint64_t> positions;
         std::string perr;
@@ -3033,42 +2753,17 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         if (!perr.empty()) throw std::runtime_error("Index.db: " + perr);
         uint64_t n_parts = positions.size() - 1;
         size_t n_chunks = ci.offsets.size();
+        const std::vector<ChunkFrame> frames = chunk_frames(ci, comp.size(), 0, n_chunks);
 
         // decompress with per-chunk bad flags
-        DevBuf d_comp, d_data, d_chunksb, d_error, d_bad;
-        d_comp.alloc(comp.size());
-        HIP_CHECK(hipMemcpyAsync(d_comp.p, comp.data(), comp.size(), hipMemcpyHostToDevice, stream));
-        d_data.alloc(ci.data_len + 16);
+        DevBuf d_error, d_bad;
         d_bad.alloc(n_chunks + 8);
         HIP_CHECK(hipMemsetAsync(d_bad.p, 0, n_chunks + 8, stream));
         d_error.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_error.p, 0, 8, stream));
-        std::vector<ChunkDesc> chunks;
-        for (size_t c = 0; c < n_chunks; c++) {
-            uint64_t off = ci.offsets[c];
-            uint64_t end = c + 1 < n_chunks ? ci.offsets[c + 1] : comp_sz;
-            ChunkDesc cd;
-            cd.comp = d_comp.as<uint8_t>() + off;
-            cd.out = d_data.as<uint8_t>() + c * (uint64_t)ci.chunk_len;
-            cd.comp_len = (uint32_t)(end - off - 4);
-            cd.out_len = (uint32_t)std::min<uint64_t>(ci.chunk_len, ci.data_len - c * (uint64_t)ci.chunk_len);
-            chunks.push_back(cd);
-        }
-        d_chunksb.alloc(chunks.size() * sizeof(ChunkDesc) + 16);
-        HIP_CHECK(hipMemcpyAsync(d_chunksb.p, chunks.data(), chunks.size() * sizeof(ChunkDesc),
-                                 hipMemcpyHostToDevice, stream));
-        if (!chunks.empty())
-            if (ci.snappy)
-                hipLaunchKernelGGL(k_snappy_decompress_chunks,
-                                   dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
-                                   stream, d_chunksb.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                                   d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                                   d_bad.as<uint8_t>(), ci.max_comp());
-            else
-                hipLaunchKernelGGL(k_lz4_decompress_wave, dim3(lz4_decomp_grid((uint32_t)chunks.size(), 1)), dim3(WAVE), 0,
-                               stream, d_chunksb.as<ChunkDesc>(), (uint32_t)chunks.size(), 1,
-                               d_error.as<unsigned long long>(), (const uint32_t*)g_crc256,
-                               d_bad.as<uint8_t>(), ci.max_comp());
+        DecodedFile dec;
+        dec.issue(ci, frames, comp, d_error, d_bad.as<uint8_t>(), stream);
+        const DevBuf& d_data = dec.data;
         std::vector<uint8_t> bad(n_chunks);
         HIP_CHECK(hipStreamSynchronize(stream));
         if (n_chunks)
@@ -3091,33 +2786,9 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         if (kept) *kept = n_kept;
         if (dropped) *dropped = n_parts - n_kept;
 
-        // schema (same resolution as compaction)
-        SchemaParams sch{};
-        std::vector<int32_t> cfh, vckw, vsf;
-        for (auto& [nm, ct] : st.regular_cols) {
-            (void)nm;
-            if (ct == "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,org.apache.cassandra.db.marshal.BytesType)") sch.n_cpx = 1;  // last regular column
-            else if (ct == "org.apache.cassandra.db.marshal.CounterColumnType") {
-                cfh.push_back(-1);
-                sch.counters = 1;
-            } else cfh.push_back(ck_type_width(ct));
-        }
-        for (auto& ct : st.clustering_types) vckw.push_back(ck_type_width(ct));
-        for (auto& [nm, ct] : st.static_cols) { (void)nm; vsf.push_back(ck_type_width(ct)); }
-        sch.n_cols = (uint32_t)cfh.size();
-        sch.n_ck = (uint32_t)vckw.size();
-        sch.n_static = (uint32_t)vsf.size();
-        DevBuf d_cf, d_ckw, d_sf;
-        d_cf.alloc(cfh.size() * 4 + 8);
-        if (!cfh.empty()) HIP_CHECK(hipMemcpyAsync(d_cf.p, cfh.data(), cfh.size() * 4, hipMemcpyHostToDevice, stream));
-        d_ckw.alloc(vckw.size() * 4 + 8);
-        if (!vckw.empty()) HIP_CHECK(hipMemcpyAsync(d_ckw.p, vckw.data(), vckw.size() * 4, hipMemcpyHostToDevice, stream));
-        d_sf.alloc(vsf.size() * 4 + 8);
-        if (!vsf.empty()) HIP_CHECK(hipMemcpyAsync(d_sf.p, vsf.data(), vsf.size() * 4, hipMemcpyHostToDevice, stream));
-        sch.col_fixed = d_cf.as<int32_t>();
-        sch.ck_w = d_ckw.as<int32_t>();
-        sch.static_fixed = d_sf.as<int32_t>();
-        sch.column_index_size = 64 * 1024;
+        const HostSchema hsch = resolve_schema(st);
+        DevSchema dsch;
+        SchemaParams sch = dsch.upload(hsch, stream);
 
         // parse kept partitions (explicit ends: gaps where partitions dropped)
         DevBuf d_kpos, d_kend, d_recs, d_rows_in;
@@ -3142,55 +2813,14 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         d_recs.alloc(n_kept * sizeof(MRec) + 32);
         d_rows_in.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
-        DevBuf p_pdm, p_pdl, p_rcnt, p_rbase, p_kaddr;
-        ParsedCols pc{};
-        p_pdm.alloc(n_kept * 8 + 8); pc.pdel_mfda = p_pdm.as<int64_t>();
-        p_pdl.alloc(n_kept * 4 + 8); pc.pdel_ldt = p_pdl.as<uint32_t>();
-        p_rcnt.alloc(n_kept * 4 + 8); pc.row_count = p_rcnt.as<uint32_t>();
-        p_rbase.alloc(n_kept * 8 + 8); pc.row_base = p_rbase.as<uint64_t>();
-        p_kaddr.alloc(n_kept * 8 + 8); pc.key_addr = p_kaddr.as<uint64_t>();
-        StaticColsBuf p_static;
-        p_static.alloc(sch.n_static ? n_kept : 1, sch.n_static);
-        pc.st = p_static.st;
-        uint32_t blocks = (uint32_t)((n_kept + 255) / 256);
-        if (n_kept) {
-            hipLaunchKernelGGL(k_parse_count, dim3(blocks), dim3(256), 0, stream,
-                               d_src.as<SrcDesc2>(), 1u, (uint32_t)n_kept, d_recs.as<MRec>(), pc,
-                               sch, d_error.as<unsigned long long>());
-            hipLaunchKernelGGL(k_widen_u32, dim3(blocks), dim3(256), 0, stream, pc.row_count,
-                               pc.row_base, n_kept);
-        }
-        uint64_t total_rows = n_kept ? exscan_u64(pc.row_base, n_kept, stream) : 0;
-        UnfColsBuf in_rows;
-        in_rows.alloc(total_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
-        DevBuf p_cpxtot, p_cpxbase;
-        uint64_t total_in_cpx = 0;
-        if (n_kept && sch.n_cpx) {
-            // complex-cell counting pass, then arena alloc (compact's B1/B2)
-            p_cpxtot.alloc(n_kept * 4 + 8);
-            pc.cpx_total = p_cpxtot.as<uint32_t>();
-            hipLaunchKernelGGL(k_parse_rows, dim3(blocks), dim3(256), 0, stream,
-                               d_src.as<SrcDesc2>(), 1u, (uint32_t)n_kept, pc, in_rows.uc, sch,
-                               d_error.as<unsigned long long>(),
-                               d_rows_in.as<unsigned long long>(), nullptr);
-            HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
-            p_cpxbase.alloc(n_kept * 8 + 8);
-            hipLaunchKernelGGL(k_widen_u32, dim3(blocks), dim3(256), 0, stream, pc.cpx_total,
-                               p_cpxbase.as<uint64_t>(), n_kept);
-            total_in_cpx = exscan_u64(p_cpxbase.as<uint64_t>(), n_kept, stream);
-            in_rows.alloc_cpx_arena(total_in_cpx);
-        }
-        if (n_kept)
-            hipLaunchKernelGGL(k_parse_rows, dim3(blocks), dim3(256), 0, stream,
-                               d_src.as<SrcDesc2>(), 1u, (uint32_t)n_kept, pc, in_rows.uc, sch,
-                               d_error.as<unsigned long long>(), d_rows_in.as<unsigned long long>(),
-                               sch.n_cpx ? p_cpxbase.as<uint64_t>() : nullptr);
-        {
-            unsigned long long e = 0;
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(&e, d_error.p, 8, hipMemcpyDeviceToHost));
-            if (e) throw std::runtime_error("scrub parse failed, code " + std::to_string(e));
-        }
+        ParsedInput parsed;
+        parse_input(parsed, d_src, 1u, n_kept, d_recs, sch, d_error, d_rows_in, false, stream);
+        const ParsedCols& pc = parsed.pc;
+        const UnfColsBuf& in_rows = parsed.rows;
+        const uint64_t total_rows = parsed.total_rows, total_in_cpx = parsed.total_cpx;
+        const uint32_t blocks = (uint32_t)((n_kept + 255) / 256);
+        if (unsigned long long e = read_dev_error(d_error, stream))
+            throw std::runtime_error("scrub parse failed, code " + std::to_string(e));
         // single source: records are already in DecoratedKey order
         KeyLut lut{};
         lut.base[0] = d_data.as<uint8_t>();
@@ -3266,12 +2896,8 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
                                d_grows.as<uint64_t>(), sch, pp, d_stats.as<OutStats>(),
                                d_error.as<unsigned long long>());
         }
-        HIP_CHECK(hipStreamSynchronize(stream));
-        {
-            unsigned long long e = 0;
-            HIP_CHECK(hipMemcpy(&e, d_error.p, 8, hipMemcpyDeviceToHost));
-            if (e) throw std::runtime_error("scrub reconcile failed, code " + std::to_string(e));
-        }
+        if (unsigned long long e = read_dev_error(d_error, stream))
+            throw std::runtime_error("scrub reconcile failed, code " + std::to_string(e));
         SerParams2 sp2{};
         sp2.sch = sch;
         sp2.hs.min_ts = st.min_timestamp == NO_TIMESTAMP ? TIMESTAMP_EPOCH : st.min_timestamp;
@@ -3280,7 +2906,6 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         write_sstable_device(opb, out_rows, n_groups, sp2, d_stats, d_tomb, tomb_cap, output_base,
                              st.key_type, st.clustering_types, st.regular_cols, st.static_cols,
                              stream, 0, ci.snappy, false, ci.chunk_len);
-        HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());
@@ -3304,8 +2929,7 @@ extern "C" int gpuc_flush(const gpuc_flush_rows* rows, const char* output_base,
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         if (!rows || rows->n_rows == 0) { set_err(error, error_len, "no rows"); return GPUC_ERR_UNSUPPORTED; }
         HIP_CHECK(hipSetDevice(device));
-        hipStream_t stream;
-        HIP_CHECK(hipStreamCreate(&stream));
+        Stream stream;
         ensure_crc_tables(stream);
         uint64_t n = rows->n_rows;
         // flatten to arenas
@@ -3418,7 +3042,6 @@ extern "C" int gpuc_flush(const gpuc_flush_rows* rows, const char* output_base,
                              "org.apache.cassandra.db.marshal.BytesType",
                              std::vector<std::string>{}, cols,
                              std::vector<std::pair<bytes, std::string>>{}, stream);
-        HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());
@@ -3581,8 +3204,7 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
             }
         }
         HIP_CHECK(hipSetDevice(device));
-        hipStream_t stream;
-        HIP_CHECK(hipStreamCreate(&stream));
+        Stream stream;
         ensure_crc_tables(stream);
         // ---- key arena + device partition sort (token, key bytes) ----
         std::vector<uint8_t> kbuf(key_bytes);
@@ -3900,7 +3522,6 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                              key_type, ck_types, regular_cols, static_cols, stream, 0,
                              S.snappy != 0, S.bti != 0,
                              checked_chunk_len_arg(S.chunk_length, CHUNK_LEN));
-        HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());
@@ -3935,8 +3556,7 @@ extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* e
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         (void)checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN);  // before any work
         HIP_CHECK(hipSetDevice(spec->device));
-        hipStream_t stream;
-        HIP_CHECK(hipStreamCreate(&stream));
+        Stream stream;
         ensure_crc_tables(stream);
         uint64_t R = spec->rows_per_sstable;
         uint64_t stride = R * (100 - spec->overlap_pct) / 100;
@@ -4112,7 +3732,6 @@ extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* e
                                  cols, scols, stream, 0, spec->snappy != 0, spec->bti != 0,
                                  checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN));
         }
-        HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());
@@ -4142,8 +3761,7 @@ extern "C" int gpuc_compress_buffer(const uint8_t* data, uint64_t len, uint32_t 
         const uint32_t n_chunks = (uint32_t)((len + cl - 1) / cl);
         if (n_chunks > offsets_cap) throw unsupported_error("offsets_cap too small");
         HIP_CHECK(hipSetDevice(device));
-        hipStream_t stream;
-        HIP_CHECK(hipStreamCreate(&stream));
+        Stream stream;
         ensure_crc_tables(stream);
         const uint32_t stride = snappy ? snp_slot_stride(cl) : lz4_slot_stride(cl);
         uint64_t total = 0;
@@ -4184,7 +3802,6 @@ extern "C" int gpuc_compress_buffer(const uint8_t* data, uint64_t len, uint32_t 
         }
         if (out_len) *out_len = total;
         if (n_chunks_out) *n_chunks_out = n_chunks;
-        HIP_CHECK(hipStreamDestroy(stream));
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());

@@ -1,0 +1,338 @@
+// PRODUCT — host-only input metadata of an sstable: CompressionInfo.db,
+// Statistics.db and Index.db parsing, chunk framing and schema resolution.
+// No HIP here: gpucompact.cpp includes it, and tests/native/sstable_meta_test.cpp
+// builds it with a plain host compiler.
+#pragma once
+#include "codec.h"
+
+#include <map>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace gpuc {
+
+using bytes = std::vector<uint8_t>;
+
+// bounds-checked big-endian reader; invariant: pos <= len
+struct HReader {
+    const uint8_t* p;
+    size_t len, pos = 0;
+    explicit HReader(const bytes& b) : p(b.data()), len(b.size()) {}
+    void need(size_t n) const { if (n > len - pos) throw std::runtime_error("short read in component"); }
+    void seek(size_t at) { if (at > len) throw std::runtime_error("short read in component"); pos = at; }
+    uint8_t u8() { need(1); return p[pos++]; }
+    uint16_t be16() { need(2); uint16_t v = ((uint16_t)p[pos] << 8) | p[pos + 1]; pos += 2; return v; }
+    uint32_t be32() { need(4); uint32_t v = 0; for (int i = 0; i < 4; i++) v = (v << 8) | p[pos + i]; pos += 4; return v; }
+    uint64_t be64() { need(8); uint64_t v = 0; for (int i = 0; i < 8; i++) v = (v << 8) | p[pos + i]; pos += 8; return v; }
+    bytes take(size_t n) { need(n); bytes b(p + pos, p + pos + n); pos += n; return b; }
+    void skip(size_t n) { need(n); pos += n; }
+    uint64_t uvint() {
+        need(1);
+        // length from the first byte's leading ones, checked before the read
+        uint8_t inv = (uint8_t)~p[pos];
+        size_t extra = inv ? (size_t)__builtin_clz((uint32_t)inv) - 24 : 8;
+        if (extra > len - pos - 1) throw std::runtime_error("vint overrun");
+        uint64_t q = pos;
+        uint64_t v = uvint_get(p, &q);
+        pos = q;
+        return v;
+    }
+};
+
+// typed failures the C ABI maps to GPUC_ERR_UNSUPPORTED / GPUC_ERR_FORMAT
+struct unsupported_error : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+struct format_error : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+static const char* const CHUNK_LEN_WHY =
+    " (supported: powers of two from 1 KiB to 64 KiB; above 64 KiB liblz4 leaves its byU16 "
+    "table and snappy splits into several 64 KiB fragments)";
+// a chunk length handed in as an ARGUMENT (0 == caller's default)
+inline uint32_t checked_chunk_len_arg(uint32_t len, uint32_t dflt) {
+    if (len == 0) return dflt;
+    if (!chunk_len_supported(len))
+        throw unsupported_error("unsupported chunk_length " + std::to_string(len) + CHUNK_LEN_WHY);
+    return len;
+}
+
+struct HCompressionInfo {
+    uint32_t chunk_len = 16384;
+    uint32_t max_compressed = 0x7FFFFFFF;
+    uint64_t data_len = 0;
+    bool snappy = false;  // SnappyCompressor (else LZ4Compressor)
+    std::vector<uint64_t> offsets;
+    // decoder sanity bound for this input's frames (codec.h)
+    uint32_t max_comp() const { return snappy ? snp_max_comp(chunk_len) : lz4_max_comp(chunk_len); }
+};
+inline HCompressionInfo parse_compression_info(const bytes& b) {
+    HReader r(b);
+    uint16_t nlen = r.be16();
+    bytes name = r.take(nlen);
+    std::string algo((char*)name.data(), name.size());
+    if (algo != "LZ4Compressor" && algo != "SnappyCompressor")
+        throw std::runtime_error("unsupported compressor " + algo + " (GPU path: LZ4/Snappy)");
+    uint32_t opts = r.be32();
+    for (uint32_t i = 0; i < opts; i++) { r.take(r.be16()); r.take(r.be16()); }
+    HCompressionInfo ci;
+    ci.snappy = algo == "SnappyCompressor";
+    ci.chunk_len = r.be32();
+    ci.max_compressed = r.be32();
+    ci.data_len = r.be64();
+    uint32_t n = r.be32();
+    // checked before the offset table is even read: nothing downstream (and
+    // no kernel) ever sees a length the codecs were not built for
+    if (!chunk_len_pow2(ci.chunk_len))
+        throw format_error("CompressionInfo.db: chunk_length " + std::to_string(ci.chunk_len) +
+                           " is not a power of two");
+    if (!chunk_len_supported(ci.chunk_len))
+        throw unsupported_error("unsupported chunk_length " + std::to_string(ci.chunk_len) +
+                                CHUNK_LEN_WHY);
+    r.need((size_t)n * 8);  // before sizing the table from an untrusted count
+    ci.offsets.resize(n);
+    for (uint32_t i = 0; i < n; i++) ci.offsets[i] = r.be64();
+    return ci;
+}
+
+// ---------------------------------------------------------------------------
+// chunk framing: Data.db is ci.offsets.size() frames, each a compressed
+// payload followed by its 4-byte CRC; frame c ends where frame c+1 starts
+// (the last at the end of the file).
+// ---------------------------------------------------------------------------
+struct ChunkFrame {
+    uint64_t off;       // file offset of the payload
+    uint32_t comp_len;  // payload bytes (CRC excluded)
+    uint32_t out_len;   // uncompressed bytes
+};
+// Everything downstream subtracts and indexes with these offsets, so the
+// whole table is checked before any of it is used.
+inline void validate_chunk_table(const HCompressionInfo& ci, uint64_t comp_file_size) {
+    const uint64_t n = ci.offsets.size();
+    if (n != ci.data_len / ci.chunk_len + (ci.data_len % ci.chunk_len ? 1 : 0))
+        throw format_error("CompressionInfo.db: " + std::to_string(n) + " chunk offsets for " +
+                           std::to_string(ci.data_len) + " bytes of chunk_length " +
+                           std::to_string(ci.chunk_len));
+    for (uint64_t c = 0; c < n; c++) {
+        uint64_t off = ci.offsets[c];
+        uint64_t end = c + 1 < n ? ci.offsets[c + 1] : comp_file_size;
+        // off + 4 <= end <= file size, without wrapping; payload length fits 32 bits
+        if (end > comp_file_size || off > end || end - off < 4 || end - off - 4 > 0xFFFFFFFFull)
+            throw format_error("CompressionInfo.db: chunk " + std::to_string(c) +
+                               " frame [" + std::to_string(off) + ", " + std::to_string(end) +
+                               ") is not inside Data.db (" + std::to_string(comp_file_size) +
+                               " bytes) in increasing order");
+    }
+}
+// frames of chunks [c_lo, c_hi)
+inline std::vector<ChunkFrame> chunk_frames(const HCompressionInfo& ci, uint64_t comp_file_size,
+                                            uint64_t c_lo, uint64_t c_hi) {
+    validate_chunk_table(ci, comp_file_size);
+    const uint64_t n = ci.offsets.size();
+    if (c_lo > c_hi || c_hi > n) throw std::runtime_error("chunk window out of range");
+    std::vector<ChunkFrame> fr;
+    fr.reserve(c_hi - c_lo);
+    for (uint64_t c = c_lo; c < c_hi; c++) {
+        uint64_t end = c + 1 < n ? ci.offsets[c + 1] : comp_file_size;
+        uint64_t left = ci.data_len - c * ci.chunk_len;
+        fr.push_back({ci.offsets[c], (uint32_t)(end - ci.offsets[c] - 4),
+                      (uint32_t)(left < ci.chunk_len ? left : ci.chunk_len)});
+    }
+    return fr;
+}
+// partitions [blo, bhi) of `positions` (n_parts + 1 uncompressed offsets, the
+// last == data_len) -> chunks [c_lo, c_hi) -> compressed bytes [comp_lo, comp_hi).
+// An empty partition window is all zeros. Whole file: [0, n_parts).
+struct ChunkWindow {
+    uint64_t c_lo = 0, c_hi = 0, comp_lo = 0, comp_hi = 0;
+};
+inline ChunkWindow chunk_window(const HCompressionInfo& ci, uint64_t comp_file_size,
+                                const std::vector<uint64_t>& positions, uint64_t blo,
+                                uint64_t bhi) {
+    validate_chunk_table(ci, comp_file_size);
+    ChunkWindow w;
+    if (blo > bhi || bhi >= positions.size()) throw std::runtime_error("partition window out of range");
+    if (blo == bhi) return w;
+    const uint64_t n = ci.offsets.size(), cl = ci.chunk_len;
+    w.c_lo = positions[blo] / cl;
+    w.c_hi = positions[bhi] / cl + (positions[bhi] % cl ? 1 : 0);
+    if (w.c_hi > n) w.c_hi = n;
+    if (w.c_lo > w.c_hi) w.c_lo = w.c_hi;
+    w.comp_lo = w.c_lo < n ? ci.offsets[w.c_lo] : comp_file_size;
+    w.comp_hi = w.c_hi < n ? ci.offsets[w.c_hi] : comp_file_size;
+    return w;
+}
+
+struct HStatistics {
+    // HEADER component
+    int64_t hdr_min_ts = TIMESTAMP_EPOCH;
+    int64_t hdr_min_ldt = DELETION_TIME_EPOCH;
+    int32_t hdr_min_ttl = 0;
+    std::string key_type;
+    std::vector<std::string> clustering_types;
+    std::vector<std::pair<bytes, std::string>> static_cols, regular_cols;
+    // STATS mins (for SerializationHeader.make of the output)
+    int64_t min_timestamp = 0, max_timestamp = 0;
+    int64_t min_ldt = NO_DELETION_TIME, max_ldt = 0;
+    int32_t min_ttl = 0, max_ttl = 0;
+    std::string partitioner;
+};
+inline HStatistics parse_statistics(const bytes& b) {
+    HReader r(b);
+    uint32_t count = r.be32();
+    r.be32();
+    std::map<uint32_t, uint32_t> toc;
+    for (uint32_t i = 0; i < count; i++) {
+        uint32_t t = r.be32();
+        uint32_t pos = r.be32();
+        toc[t] = pos;
+    }
+    r.be32();
+    HStatistics st;
+    if (toc.count(0)) {
+        HReader v(b);
+        v.seek(toc[0]);
+        uint16_t n = v.be16();
+        bytes s = v.take(n);
+        st.partitioner.assign((char*)s.data(), s.size());
+    }
+    if (!toc.count(3)) throw std::runtime_error("Statistics.db missing HEADER component");
+    {
+        HReader h(b);
+        h.seek(toc[3]);
+        st.hdr_min_ts = (int64_t)h.uvint() + TIMESTAMP_EPOCH;
+        st.hdr_min_ldt = (int64_t)(int32_t)(uint32_t)h.uvint() + DELETION_TIME_EPOCH;
+        st.hdr_min_ttl = (int32_t)(uint32_t)h.uvint();
+        auto rstr = [&]() { size_t n = (size_t)h.uvint(); bytes s = h.take(n); return std::string((char*)s.data(), s.size()); };
+        st.key_type = rstr();
+        size_t nct = (size_t)h.uvint();
+        for (size_t i = 0; i < nct; i++) st.clustering_types.push_back(rstr());
+        for (auto* cols : {&st.static_cols, &st.regular_cols}) {
+            size_t nc = (size_t)h.uvint();
+            for (size_t i = 0; i < nc; i++) {
+                size_t nn = (size_t)h.uvint();
+                bytes name = h.take(nn);
+                cols->push_back({name, rstr()});
+            }
+        }
+    }
+    if (toc.count(2)) {
+        HReader s(b);
+        s.seek(toc[2]);
+        for (int hh = 0; hh < 2; hh++) { uint32_t n = s.be32(); s.skip((size_t)n * 16); }
+        s.skip(12);
+        st.min_timestamp = (int64_t)s.be64();
+        st.max_timestamp = (int64_t)s.be64();
+        st.min_ldt = ldt_long(s.be32());
+        st.max_ldt = ldt_long(s.be32());
+        st.min_ttl = (int32_t)s.be32();
+        st.max_ttl = (int32_t)s.be32();
+    }
+    return st;
+}
+
+// Index.db -> partition positions (host thread; validates non-indexed entries)
+inline void parse_index_positions(const bytes& ib, uint64_t data_len,
+                                  std::vector<uint64_t>& positions,
+                                  std::vector<uint64_t>* entry_offs, std::string& err) {
+    try {
+        HReader r(ib);
+        positions.reserve(ib.size() / 18 + 2);
+        if (entry_offs) entry_offs->reserve(ib.size() / 18 + 2);
+        while (r.pos < r.len) {
+            if (entry_offs) entry_offs->push_back(r.pos);
+            uint16_t klen = r.be16();
+            r.skip(klen);
+            uint64_t pos = r.uvint();
+            uint64_t promoted = r.uvint();
+            r.skip(promoted);
+            if (pos >= data_len || (!positions.empty() && pos <= positions.back()))
+                throw std::runtime_error("Index.db positions not increasing/in range");
+            positions.push_back(pos);
+        }
+        positions.push_back(data_len);
+    } catch (const std::exception& e) {
+        err = e.what();
+    }
+}
+
+// ---------------------------------------------------------------------------
+// schema: marshal type strings -> the widths the parse kernels walk with
+// ---------------------------------------------------------------------------
+// marshal type string -> clustering component width (-1 variable)
+inline int32_t ck_type_width(const std::string& t) {
+    if (t == "org.apache.cassandra.db.marshal.LongType") return 8;
+    if (t == "org.apache.cassandra.db.marshal.Int32Type") return 4;
+    if (t == "org.apache.cassandra.db.marshal.UTF8Type" ||
+        t == "org.apache.cassandra.db.marshal.AsciiType" ||
+        t == "org.apache.cassandra.db.marshal.BytesType")
+        return -1;
+    throw std::runtime_error("unsupported clustering type " + t);
+}
+
+struct HostSchema {
+    std::vector<int32_t> col_fixed;     // SIMPLE regular columns only
+    std::vector<int32_t> ck_widths;     // per clustering column
+    std::vector<int32_t> static_fixed;  // per static column
+    uint32_t n_cpx = 0;                 // one complex (map<blob,blob>) column, last
+    bool counters = false;              // counter table (every column CounterColumnType)
+};
+// The one resolver: rejects every layout the engine cannot walk.
+inline HostSchema resolve_schema(const HStatistics& st) {
+    HostSchema hs;
+    const auto& rcols = st.regular_cols;
+    for (size_t ci = 0; ci < rcols.size(); ci++) {
+        const std::string& ct = rcols[ci].second;
+        if (ct == "org.apache.cassandra.db.marshal.LongType") hs.col_fixed.push_back(8);
+        else if (ct == "org.apache.cassandra.db.marshal.Int32Type") hs.col_fixed.push_back(4);
+        else if (ct == "org.apache.cassandra.db.marshal.BytesType" ||
+                 ct == "org.apache.cassandra.db.marshal.UTF8Type" ||
+                 ct == "org.apache.cassandra.db.marshal.AsciiType")
+            hs.col_fixed.push_back(-1);
+        else if (ct == "org.apache.cassandra.db.marshal.CounterColumnType") {
+            hs.col_fixed.push_back(-1);
+            hs.counters = true;
+        }
+        else if (ct == "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,org.apache.cassandra.db.marshal.BytesType)") {
+            // one complex column, and it must be the LAST regular column
+            // (engine layout constraint; the generator names it 'zm' so
+            // name order puts it last)
+            if (hs.n_cpx || ci + 1 != rcols.size())
+                throw std::runtime_error("at most one complex column, as the last regular column");
+            hs.n_cpx = 1;
+        } else {
+            throw std::runtime_error("unsupported column type " + ct);
+        }
+    }
+    if (hs.counters) {
+        // counter tables hold only counter columns (CreateTableStatement
+        // forbids mixing); complex/static columns are rejected with them
+        if (hs.col_fixed.size() != rcols.size() || hs.n_cpx)
+            throw std::runtime_error("counter tables must be all-counter columns");
+        for (auto& cp : rcols)
+            if (cp.second != "org.apache.cassandra.db.marshal.CounterColumnType")
+                throw std::runtime_error("counter tables must be all-counter columns");
+        if (!st.static_cols.empty())
+            throw std::runtime_error("static columns with counters unsupported");
+    }
+    for (auto& t : st.clustering_types) hs.ck_widths.push_back(ck_type_width(t));
+    for (auto& sc : st.static_cols) {
+        const std::string& ct2 = sc.second;
+        if (ct2 == "org.apache.cassandra.db.marshal.LongType") hs.static_fixed.push_back(8);
+        else if (ct2 == "org.apache.cassandra.db.marshal.Int32Type") hs.static_fixed.push_back(4);
+        else if (ct2 == "org.apache.cassandra.db.marshal.BytesType" ||
+                 ct2 == "org.apache.cassandra.db.marshal.UTF8Type" ||
+                 ct2 == "org.apache.cassandra.db.marshal.AsciiType")
+            hs.static_fixed.push_back(-1);
+        else throw std::runtime_error("unsupported static column type " + ct2);
+    }
+    if (hs.static_fixed.size() > 63)
+        throw std::runtime_error("1..63 static columns supported");
+    if (hs.ck_widths.size() > 32)
+        throw std::runtime_error("at most 32 clustering columns supported");
+    return hs;
+}
+
+}  // namespace gpuc

@@ -1,0 +1,379 @@
+// CPU test of cassandra_amd/csrc/sstable_meta.h: the host-only input metadata
+// parsers, chunk framing and schema resolution, on well-formed sstables and on
+// damaged copies built in memory. Plain host C++, no HIP.
+//
+// usage: sstable_meta_test <base>@<expected schema> ... golden=<base> ...
+//   expected schema: cols=<w,..>;ck=<w,..>;st=<w,..>;cpx=<n>;ctr=<0|1>
+#include "../../cassandra_amd/csrc/sstable_meta.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <functional>
+#include <sstream>
+
+using namespace gpuc;
+
+static int g_checks = 0;
+#define CHECK(cond, ...)                                                       \
+    do {                                                                       \
+        g_checks++;                                                            \
+        if (!(cond)) {                                                         \
+            fprintf(stderr, "FAIL %s:%d: %s: ", __FILE__, __LINE__, #cond);    \
+            fprintf(stderr, __VA_ARGS__);                                      \
+            fprintf(stderr, "\n");                                             \
+            exit(1);                                                           \
+        }                                                                      \
+    } while (0)
+
+static bytes slurp(const std::string& path) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path.c_str()); exit(2); }
+    bytes b;
+    uint8_t buf[65536];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof(buf), f)) > 0) b.insert(b.end(), buf, buf + n);
+    fclose(f);
+    return b;
+}
+static uint64_t size_of(const std::string& path) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path.c_str()); exit(2); }
+    fseek(f, 0, SEEK_END);
+    long n = ftell(f);
+    fclose(f);
+    return (uint64_t)n;
+}
+static void be(bytes& o, uint64_t v, int n) {
+    for (int i = n - 1; i >= 0; i--) o.push_back((uint8_t)(v >> (8 * i)));
+}
+static bytes serialize_ci(const HCompressionInfo& ci, const std::vector<uint64_t>& offsets) {
+    bytes o;
+    std::string name = ci.snappy ? "SnappyCompressor" : "LZ4Compressor";
+    be(o, name.size(), 2);
+    o.insert(o.end(), name.begin(), name.end());
+    be(o, 0, 4);
+    be(o, ci.chunk_len, 4);
+    be(o, ci.max_compressed, 4);
+    be(o, ci.data_len, 8);
+    be(o, offsets.size(), 4);
+    for (uint64_t x : offsets) be(o, x, 8);
+    return o;
+}
+static std::vector<int32_t> ints(const std::string& s) {
+    std::vector<int32_t> v;
+    std::stringstream ss(s);
+    std::string t;
+    while (std::getline(ss, t, ','))
+        if (!t.empty()) v.push_back(atoi(t.c_str()));
+    return v;
+}
+
+// what kind of exception a callable ends with: 'f' format_error, 'u'
+// unsupported_error, 'r' another std::exception, '-' none
+static char thrown(const std::function<void()>& fn) {
+    try { fn(); }
+    catch (const format_error&) { return 'f'; }
+    catch (const unsupported_error&) { return 'u'; }
+    catch (const std::exception&) { return 'r'; }
+    return '-';
+}
+
+// the reader's bound check holds for lengths near 2^64 (pos + n would wrap)
+static void check_reader() {
+    bytes b(16, 0);
+    b[15] = 0xF0;  // a 5-byte vint cut after its first byte
+    HReader r(b);
+    r.skip(5);
+    for (size_t n : {~(size_t)0, ~(size_t)0 - 4, ~(size_t)0 - 5, ~(size_t)0 - 15, (size_t)12}) {
+        CHECK(thrown([&] { r.skip(n); }) == 'r', "skip(%zu) accepted", n);
+        CHECK(thrown([&] { r.take(n); }) == 'r', "take(%zu) accepted", n);
+        CHECK(r.pos == 5, "pos moved to %zu", r.pos);
+    }
+    CHECK(thrown([&] { r.seek(17); }) == 'r' && r.pos == 5, "seek past the end");
+    r.skip(10);
+    CHECK(thrown([&] { r.uvint(); }) == 'r' && r.pos == 15, "cut vint accepted");
+    r.skip(1);
+    CHECK(r.pos == 16 && thrown([&] { r.u8(); }) == 'r', "read at the end");
+    r.seek(16);
+    r.skip(0);
+}
+
+struct Input {
+    std::string base;
+    bytes ci_b, st_b, ix_b;
+    uint64_t data_size = 0;
+    HCompressionInfo ci;
+    HStatistics st;
+    std::vector<uint64_t> positions;
+};
+
+static Input load(const std::string& base) {
+    Input in;
+    in.base = base;
+    in.ci_b = slurp(base + "-CompressionInfo.db");
+    in.st_b = slurp(base + "-Statistics.db");
+    in.ix_b = slurp(base + "-Index.db");
+    in.data_size = size_of(base + "-Data.db");
+    in.ci = parse_compression_info(in.ci_b);
+    in.st = parse_statistics(in.st_b);
+    std::string err;
+    parse_index_positions(in.ix_b, in.ci.data_len, in.positions, nullptr, err);
+    CHECK(err.empty(), "%s: %s", base.c_str(), err.c_str());
+    return in;
+}
+
+static void check_well_formed(const Input& in) {
+    const char* b = in.base.c_str();
+    const auto& pos = in.positions;
+    const auto& ci = in.ci;
+    // positions: strictly increasing, ending at data_len
+    CHECK(pos.size() >= 2, "%s: no partitions", b);
+    for (size_t i = 1; i < pos.size(); i++) CHECK(pos[i - 1] < pos[i], "%s: position %zu", b, i);
+    CHECK(pos.back() == ci.data_len, "%s", b);
+    // whole-file frames tile [first offset, file size) and sum to data_len
+    const uint64_t n = ci.offsets.size();
+    auto fr = chunk_frames(ci, in.data_size, 0, n);
+    CHECK(fr.size() == n && n > 0, "%s", b);
+    uint64_t at = ci.offsets[0], unc = 0;
+    for (uint64_t c = 0; c < n; c++) {
+        CHECK(fr[c].off == at, "%s: chunk %llu", b, (unsigned long long)c);
+        CHECK(fr[c].out_len > 0 && fr[c].out_len <= ci.chunk_len, "%s", b);
+        CHECK(fr[c].out_len == ci.chunk_len || c + 1 == n, "%s: short chunk %llu", b,
+              (unsigned long long)c);
+        at += (uint64_t)fr[c].comp_len + 4;
+        unc += fr[c].out_len;
+    }
+    CHECK(at == in.data_size, "%s: frames end at %llu of %llu", b, (unsigned long long)at,
+          (unsigned long long)in.data_size);
+    CHECK(unc == ci.data_len, "%s", b);
+    // partition windows cover their positions; their frames tile the byte window
+    const uint64_t np = pos.size() - 1;
+    const uint64_t picks[][2] = {{0, np}, {0, 1}, {np - 1, np}, {np / 3, np / 3 + 1},
+                                 {np / 3, 2 * np / 3 + 1}, {np / 2, np}, {1 % np, np}};
+    for (auto& pk : picks) {
+        uint64_t i = pk[0], j = pk[1];
+        if (i >= j || j > np) continue;
+        ChunkWindow w = chunk_window(ci, in.data_size, pos, i, j);
+        CHECK(w.c_lo < w.c_hi && w.c_hi <= n, "%s [%llu,%llu)", b, (unsigned long long)i,
+              (unsigned long long)j);
+        CHECK(w.c_lo * ci.chunk_len <= pos[i], "%s", b);
+        CHECK(w.c_hi * ci.chunk_len >= pos[j] || w.c_hi == n, "%s", b);
+        CHECK((w.c_lo + 1) * ci.chunk_len > pos[i], "%s: window starts early", b);
+        CHECK((w.c_hi - 1) * ci.chunk_len < pos[j], "%s: window ends late", b);
+        CHECK(w.comp_lo == ci.offsets[w.c_lo], "%s", b);
+        CHECK(w.comp_hi == (w.c_hi < n ? ci.offsets[w.c_hi] : in.data_size), "%s", b);
+        auto wf = chunk_frames(ci, in.data_size, w.c_lo, w.c_hi);
+        uint64_t a2 = w.comp_lo;
+        for (auto& f : wf) { CHECK(f.off == a2, "%s", b); a2 += (uint64_t)f.comp_len + 4; }
+        CHECK(a2 == w.comp_hi, "%s", b);
+    }
+    ChunkWindow whole = chunk_window(ci, in.data_size, pos, 0, np);
+    CHECK(whole.c_lo == 0 && whole.c_hi == n && whole.comp_lo == ci.offsets[0] &&
+          whole.comp_hi == in.data_size, "%s: whole-file window", b);
+    ChunkWindow empty = chunk_window(ci, in.data_size, pos, np / 2, np / 2);
+    CHECK(!empty.c_lo && !empty.c_hi && !empty.comp_lo && !empty.comp_hi, "%s", b);
+    CHECK(thrown([&] { chunk_window(ci, in.data_size, pos, 0, np + 1); }) == 'r', "%s", b);
+    CHECK(thrown([&] { chunk_frames(ci, in.data_size, 0, n + 1); }) == 'r', "%s", b);
+}
+
+static void check_schema(const Input& in, const std::string& want) {
+    HostSchema hs = resolve_schema(in.st);
+    std::stringstream ss(want);
+    std::string kv;
+    while (std::getline(ss, kv, ';')) {
+        size_t eq = kv.find('=');
+        std::string k = kv.substr(0, eq), v = kv.substr(eq + 1);
+        if (k == "cols") CHECK(hs.col_fixed == ints(v), "%s cols", in.base.c_str());
+        else if (k == "ck") CHECK(hs.ck_widths == ints(v), "%s ck", in.base.c_str());
+        else if (k == "st") CHECK(hs.static_fixed == ints(v), "%s st", in.base.c_str());
+        else if (k == "cpx") CHECK(hs.n_cpx == (uint32_t)atoi(v.c_str()), "%s cpx", in.base.c_str());
+        else if (k == "ctr") CHECK(hs.counters == (atoi(v.c_str()) != 0), "%s ctr", in.base.c_str());
+        else CHECK(false, "bad expectation key %s", k.c_str());
+    }
+}
+
+// every damaged offset table is a format_error from both entry points
+static void expect_bad_frames(const Input& in, const std::vector<uint64_t>& offs, const char* what) {
+    HCompressionInfo ci = parse_compression_info(serialize_ci(in.ci, offs));
+    char a = thrown([&] { chunk_frames(ci, in.data_size, 0, ci.offsets.size()); });
+    char b = thrown([&] { chunk_window(ci, in.data_size, in.positions, 0, in.positions.size() - 1); });
+    CHECK(a == 'f' && b == 'f', "%s: %s -> '%c' '%c'", in.base.c_str(), what, a, b);
+}
+
+static void check_damaged_compression_info(const Input& in) {
+    const auto& good = in.ci.offsets;
+    const size_t n = good.size();
+    {   // the serializer used here reproduces the good table
+        HCompressionInfo ci = parse_compression_info(serialize_ci(in.ci, good));
+        CHECK(ci.offsets == good && ci.data_len == in.ci.data_len, "%s", in.base.c_str());
+        CHECK(thrown([&] { chunk_frames(ci, in.data_size, 0, n); }) == '-', "%s", in.base.c_str());
+    }
+    auto v = good;
+    std::swap(v[0], v[1]);
+    expect_bad_frames(in, v, "first two offsets swapped");
+    v = good;
+    std::swap(v[n - 2], v[n - 1]);
+    expect_bad_frames(in, v, "last two offsets swapped");
+    v = good;
+    v[n - 1] = in.data_size + 1;
+    expect_bad_frames(in, v, "last offset past the file");
+    v[n - 1] = ~0ull - 1;
+    expect_bad_frames(in, v, "last offset near 2^64");
+    v = good;
+    v[n - 1] = in.data_size - 3;
+    expect_bad_frames(in, v, "last frame shorter than its CRC");
+    v = good;
+    v.pop_back();
+    expect_bad_frames(in, v, "one offset fewer");
+    v = good;
+    v.push_back(in.data_size - 4);
+    expect_bad_frames(in, v, "one offset more");
+    v = good;
+    v[1] = v[0] + 3;
+    expect_bad_frames(in, v, "end - off < 4");
+    v = good;
+    v[1] = v[0];
+    expect_bad_frames(in, v, "equal offsets");
+    // a Data.db shorter than the table says
+    char c = thrown([&] { chunk_frames(in.ci, good[n - 1] + 3, 0, n); });
+    CHECK(c == 'f', "%s: short Data.db -> '%c'", in.base.c_str(), c);
+    // an offset count the file cannot hold is a short read, not an allocation
+    bytes big = serialize_ci(in.ci, good);
+    size_t cnt_at = big.size() - 8 * n - 4;
+    for (int i = 0; i < 4; i++) big[cnt_at + i] = 0xFF;
+    c = thrown([&] { parse_compression_info(big); });
+    CHECK(c == 'r', "%s: huge chunk count -> '%c'", in.base.c_str(), c);
+}
+
+static std::string index_err(const bytes& ib, uint64_t data_len) {
+    std::vector<uint64_t> positions;
+    std::string err;
+    parse_index_positions(ib, data_len, positions, nullptr, err);
+    return err;
+}
+
+static void check_damaged_index(const Input& in) {
+    const uint64_t dl = in.ci.data_len;
+    {   // promoted-index size of 2^64 - 1: pos + n must not wrap past the check
+        bytes ib = {0, 1, 'k', 0};
+        ib.insert(ib.end(), 9, 0xFF);
+        ib.insert(ib.end(), in.ix_b.begin(), in.ix_b.end());
+        CHECK(!index_err(ib, dl).empty(), "promoted size 2^64-1 accepted");
+    }
+    for (uint64_t promoted : {~0ull - 3, 1ull << 63, (1ull << 32) + 5}) {
+        bytes ib = {0, 1, 'k', 0, 0xFF};
+        be(ib, promoted, 8);
+        ib.insert(ib.end(), 64, 0);
+        CHECK(!index_err(ib, dl).empty(), "promoted size %llu accepted",
+              (unsigned long long)promoted);
+    }
+    {   // key length running past the end
+        bytes ib = {0xFF, 0xFF, 'a', 'b', 'c'};
+        CHECK(!index_err(ib, dl).empty(), "long key accepted");
+        bytes ib2(in.ix_b.begin(), in.ix_b.end());
+        ib2.push_back(0);
+        ib2.push_back(9);
+        ib2.push_back('x');
+        CHECK(!index_err(ib2, dl).empty(), "trailing long key accepted");
+    }
+    {   // a vint whose continuation bytes are missing
+        bytes ib = {0, 1, 'k', 0xF0, 1};
+        CHECK(!index_err(ib, dl).empty(), "cut vint accepted");
+    }
+}
+
+static void check_damaged_statistics(const Input& in) {
+    const bytes& good = in.st_b;
+    HReader r(good);
+    uint32_t count = r.be32();
+    r.be32();
+    size_t hdr_slot = 0, hdr_pos = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        uint32_t t = r.be32();
+        size_t slot = r.pos;
+        uint32_t p = r.be32();
+        for (uint32_t bad : {(uint32_t)good.size() + 1, (uint32_t)good.size() + 100, 0xFFFFFFFFu}) {
+            // a table-of-contents position past the end, for every component
+            bytes b = good;
+            for (int k = 0; k < 4; k++) b[slot + k] = (uint8_t)(bad >> (8 * (3 - k)));
+            char c = thrown([&] { parse_statistics(b); });
+            // components 1 (COMPACTION) is not read by the parser
+            CHECK(c == (t == 1 ? '-' : 'r'), "%s: toc[%u]=%u -> '%c'", in.base.c_str(), t, bad, c);
+        }
+        if (t == 3) { hdr_slot = slot; hdr_pos = p; }
+    }
+    CHECK(hdr_slot, "%s: no HEADER component", in.base.c_str());
+    // the key type name's length: first a length that runs past the end of a
+    // truncated file, then 2^64 - 1
+    HReader h(good);
+    h.seek(hdr_pos);
+    h.uvint(); h.uvint(); h.uvint();
+    size_t len_at = h.pos;
+    CHECK(good[len_at] < 0x80 && good[len_at] > 8, "%s: unexpected key type length", in.base.c_str());
+    bytes b(good.begin(), good.begin() + len_at + 1 + 8);
+    char c = thrown([&] { parse_statistics(b); });
+    CHECK(c == 'r', "%s: type name past the end -> '%c'", in.base.c_str(), c);
+    b = good;
+    for (int k = 0; k < 9; k++) b[len_at + k] = 0xFF;
+    c = thrown([&] { parse_statistics(b); });
+    CHECK(c == 'r', "%s: type name of 2^64-1 bytes -> '%c'", in.base.c_str(), c);
+}
+
+// every prefix of each file either parses or ends in an exception
+static void check_truncations(const Input& in) {
+    size_t thrown_ci = 0, thrown_st = 0, err_ix = 0;
+    for (size_t n = 0; n <= std::min<size_t>(in.ci_b.size(), 512); n++) {
+        bytes b(in.ci_b.begin(), in.ci_b.begin() + n);
+        char c = thrown([&] {
+            HCompressionInfo ci = parse_compression_info(b);
+            chunk_frames(ci, in.data_size, 0, ci.offsets.size());
+        });
+        thrown_ci += c != '-';
+        CHECK(c != '-' || n == in.ci_b.size(), "%s: CompressionInfo.db cut at %zu accepted",
+              in.base.c_str(), n);
+    }
+    for (size_t n = 0; n <= std::min<size_t>(in.st_b.size(), 512); n++) {
+        bytes b(in.st_b.begin(), in.st_b.begin() + n);
+        thrown_st += thrown([&] { resolve_schema(parse_statistics(b)); }) != '-';
+    }
+    for (size_t n = 0; n <= std::min<size_t>(in.ix_b.size(), 512); n++) {
+        bytes b(in.ix_b.begin(), in.ix_b.begin() + n);
+        err_ix += !index_err(b, in.ci.data_len).empty();
+    }
+    // the table of contents and header sit in the first bytes of Statistics.db
+    CHECK(thrown_ci > 0 && thrown_st > 16 && err_ix > 0, "%s: truncations %zu %zu %zu",
+          in.base.c_str(), thrown_ci, thrown_st, err_ix);
+}
+
+int main(int argc, char** argv) {
+    int n_damaged = 0, n_inputs = 0;
+    check_reader();
+    for (int a = 1; a < argc; a++) {
+        std::string arg = argv[a];
+        if (arg.compare(0, 7, "golden=") == 0) {
+            // reference-written fixtures: everything parses and frames tile
+            Input in = load(arg.substr(7));
+            check_well_formed(in);
+            char c = thrown([&] { resolve_schema(in.st); });
+            CHECK(c == '-', "%s: schema refused", in.base.c_str());
+            check_truncations(in);
+            continue;
+        }
+        size_t at = arg.find('@');
+        CHECK(at != std::string::npos, "argument %s", arg.c_str());
+        Input in = load(arg.substr(0, at));
+        check_well_formed(in);
+        check_schema(in, arg.substr(at + 1));
+        check_truncations(in);
+        check_damaged_index(in);
+        check_damaged_statistics(in);
+        if (in.ci.offsets.size() >= 3) {
+            check_damaged_compression_info(in);
+            n_damaged++;
+        }
+        n_inputs++;
+    }
+    CHECK(n_inputs > 0 && n_damaged > 0, "no input with three chunks or more");
+    printf("OK %d checks over %d inputs\n", g_checks, n_inputs);
+    return 0;
+}
