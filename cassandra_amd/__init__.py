@@ -242,6 +242,17 @@ class GpucCpxCell(ctypes.Structure):
     ]
 
 
+class GpucCpxCol(ctypes.Structure):
+    """One complex column of one row (gpuc_cpx_col)."""
+    _fields_ = [
+        ("present", ctypes.c_uint8),
+        ("del_mfda", ctypes.c_int64),
+        ("del_ldt", ctypes.c_uint32),
+        ("n_cells", ctypes.c_uint32),
+        ("cells", ctypes.POINTER(GpucCpxCell)),
+    ]
+
+
 class GpucUnfiltered(ctypes.Structure):
     _fields_ = [
         ("kind", ctypes.c_uint8),
@@ -262,6 +273,9 @@ class GpucUnfiltered(ctypes.Structure):
         ("cpx_del_ldt", ctypes.c_uint32),
         ("n_cpx_cells", ctypes.c_uint32),
         ("cpx_cells", ctypes.POINTER(GpucCpxCell)),
+        # non-NULL: schema.n_cpx entries in header order (the legacy
+        # single-column fields above are then ignored)
+        ("cpx_cols", ctypes.POINTER(GpucCpxCol)),
     ]
 
 
@@ -482,22 +496,41 @@ def _parse_memdump(data):
             r.bufs.append(cells)
             U.cells = cells
             si = 0
+            # one map column rides in the legacy fields; several go through
+            # cpx_cols, one entry per map column in header order
+            xcols = None
+            if n_cpx > 1:
+                xcols = (GpucCpxCol * n_cpx)()
+                r.bufs.append(xcols)
+                U.cpx_cols = xcols
+            xi = 0
             for i in range(n_cols):
                 if i in cpx_idx:
                     has = r.u8()
-                    U.has_cpx = has
+                    dm, dl, nc, xc = INT64_MIN, LDT_NONE, 0, None
                     if has:
-                        U.cpx_del_mfda = r.i64()
-                        U.cpx_del_ldt = r.u32()
+                        dm = r.i64()
+                        dl = r.u32()
                         nc = r.u32()
-                        U.n_cpx_cells = nc
                         xc = (GpucCpxCell * max(nc, 1))()
                         r.bufs.append(xc)
-                        U.cpx_cells = xc
                         for e in range(nc):
                             r.cell_into(xc[e].cell)
                             path = r.blob()
                             xc[e].path, xc[e].path_len = r.ptr(path)
+                    if xcols is None:
+                        U.has_cpx = has
+                        if has:
+                            U.cpx_del_mfda, U.cpx_del_ldt, U.n_cpx_cells = dm, dl, nc
+                            U.cpx_cells = xc
+                    else:
+                        X = xcols[xi]
+                        X.present = has
+                        X.del_mfda, X.del_ldt, X.n_cells = dm, dl, nc
+                        if has:
+                            X.cells = xc
+                            U.has_cpx = 1
+                    xi += 1
                 else:
                     r.cell_into(cells[si])
                     si += 1

@@ -91,11 +91,15 @@ struct UnfCols {
     uint64_t* ck_addr;
     uint32_t* ck_len;
     uint8_t* ck_count;
-    // ONE complex column (MapType(BytesType,BytesType)), the LAST regular
-    // column when SchemaParams.n_cpx == 1 (ComplexColumnData.java:47): a
-    // per-row complexDeletion + a [cpx_start, cpx_start+cpx_count) segment
-    // of path-ordered cells in the CpxCells arena. PF_HAS_CPX marks column
-    // presence (deletion-only columns have cpx_count == 0).
+    // complex columns (MapType(BytesType,BytesType)), the LAST
+    // SchemaParams.n_cpx regular columns (ComplexColumnData.java:47), strided
+    // by n_cpx: index = row_o * n_cpx + x (n_cpx == 1 degenerates to one
+    // entry per row). Per (row, column): presence, a complexDeletion and a
+    // [cpx_start, cpx_start+cpx_count) segment of path-ordered cells in the
+    // shared CpxCells arena; a row's segments lie consecutively in header
+    // order. PF_HAS_CPX = any column present; a present column may have a
+    // deletion and no cells, or (as parsed) neither.
+    uint8_t* cpx_present;
     int64_t* cpx_del_mfda;
     uint32_t* cpx_del_ldt;
     uint64_t* cpx_start;

@@ -615,7 +615,7 @@ struct UnfColsBuf {
     DevBuf ck, rkind, flags, live_ts, live_ttl, live_let, rdel_mfda, rdel_ldt,
         start_mfda, start_ldt, cell_ts, cell_ldt, cell_ttl, val_addr, val_len, ck_addr, ck_len,
         cell_flags, ck_count;
-    DevBuf cpx_del_mfda, cpx_del_ldt, cpx_start, cpx_count;          // per row
+    DevBuf cpx_present, cpx_del_mfda, cpx_del_ldt, cpx_start, cpx_count;  // per (row, complex column)
     DevBuf cx_ts, cx_ldt, cx_ttl, cx_flags, cx_pa, cx_pl, cx_va, cx_vl;  // cell arena
     UnfCols uc{};
     // cell arena sized AFTER the counting pass (arena capacity = total
@@ -640,8 +640,10 @@ struct UnfColsBuf {
         val_addr.alloc(nc * 8); val_len.alloc(nc * 4); cell_flags.alloc(nc);
         ck_addr.alloc(nk * 8); ck_len.alloc(nk * 4); ck_count.alloc(n);
         if (n_cpx) {
-            cpx_del_mfda.alloc(n * 8); cpx_del_ldt.alloc(n * 4);
-            cpx_start.alloc(n * 8); cpx_count.alloc(n * 4);
+            uint64_t nx = n * n_cpx;
+            cpx_present.alloc(nx);
+            cpx_del_mfda.alloc(nx * 8); cpx_del_ldt.alloc(nx * 4);
+            cpx_start.alloc(nx * 8); cpx_count.alloc(nx * 4);
         }
         uc = UnfCols{ck.as<uint64_t>(), rkind.as<uint8_t>(), flags.as<uint8_t>(),
                      live_ts.as<int64_t>(), live_ttl.as<int32_t>(), live_let.as<int64_t>(),
@@ -651,6 +653,7 @@ struct UnfColsBuf {
                      cell_flags.as<uint8_t>(),
                      ck_addr.as<uint64_t>(), ck_len.as<uint32_t>(), ck_count.as<uint8_t>()};
         if (n_cpx) {
+            uc.cpx_present = cpx_present.as<uint8_t>();
             uc.cpx_del_mfda = cpx_del_mfda.as<int64_t>();
             uc.cpx_del_ldt = cpx_del_ldt.as<uint32_t>();
             uc.cpx_start = cpx_start.as<uint64_t>();
@@ -1065,7 +1068,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     {
         uint64_t blocks = (n_groups + 255) / 256;
         hipLaunchKernelGGL(k_collect_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, opb.op,
-                           rows.uc, n_groups, sp.sch.n_cols, d_stats.as<OutStats>(),
+                           rows.uc, n_groups, sp.sch.n_cols, sp.sch.n_cpx, d_stats.as<OutStats>(),
                            d_tomb.as<uint32_t>(), tomb_cap);
     }
 
@@ -2621,14 +2624,35 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         Stream stream;
         ensure_crc_tables(stream);
         std::string base = input_base;
-        bytes index_data = read_file(base + "-Index.db");
+        auto exists = [](const std::string& p) { return access(p.c_str(), F_OK) == 0; };
+        const bool da = exists(base + "-Partitions.db") && !exists(base + "-Index.db");
         HCompressionInfo ci = parse_compression_info(read_file(base + "-CompressionInfo.db"));
         HStatistics st = parse_statistics(read_file(base + "-Statistics.db"));
         bytes comp = read_file(base + "-Data.db");
         std::vector<uint64_t> positions;
-        std::string perr;
-        parse_index_positions(index_data, ci.data_len, positions, nullptr, perr);
-        if (!perr.empty()) throw std::runtime_error("Index.db: " + perr);
+        if (da) {
+            // `da` sstables: positions from the Partitions.db trie, as the
+            // compaction front end reads them (DFS order == data order),
+            // held to the same bounds parse_index_positions enforces
+            bytes pf = read_file(base + "-Partitions.db");
+            bytes rf = read_file(base + "-Rows.db");
+            bti::bytes pfb(pf.begin(), pf.end());
+            bti::bytes rfb(rf.begin(), rf.end());
+            auto bp = bti::read_bti_partitions(pfb);
+            for (auto& e : bp.entries) {
+                uint64_t pos = e.idxpos < 0 ? (uint64_t)~e.idxpos
+                                            : bti::row_index_data_pos(rfb, (uint64_t)e.idxpos);
+                if (pos >= ci.data_len || (!positions.empty() && pos <= positions.back()))
+                    throw std::runtime_error("Partitions.db positions not increasing/in range");
+                positions.push_back(pos);
+            }
+            positions.push_back(ci.data_len);
+        } else {
+            bytes index_data = read_file(base + "-Index.db");
+            std::string perr;
+            parse_index_positions(index_data, ci.data_len, positions, nullptr, perr);
+            if (!perr.empty()) throw std::runtime_error("Index.db: " + perr);
+        }
         uint64_t n_parts = positions.size() - 1;
         const std::vector<ChunkFrame> frames = chunk_frames(ci, comp.size(), 0, ci.offsets.size());
 
@@ -3009,7 +3033,8 @@ extern "C" int gpuc_flush(const gpuc_flush_rows* rows, const char* output_base,
         uint32_t tomb_cap = (uint32_t)std::min<uint64_t>(n * 3 + 1024, 400000000ull);
         d_tomb.alloc((uint64_t)tomb_cap * 4);
         hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op,
-                           urows.uc, n, 1u, d_stats.as<OutStats>(), d_tomb.as<uint32_t>(), tomb_cap);
+                           urows.uc, n, 1u, 0u, d_stats.as<OutStats>(), d_tomb.as<uint32_t>(),
+                           tomb_cap);
         OutStats hs0;
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipMemcpy(&hs0, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
@@ -3113,6 +3138,22 @@ static int h_unf_cmp(const gpuc_unfiltered& a, const gpuc_unfiltered& b,
     return h_bk_comparison(a.kind) - h_bk_comparison(b.kind);
 }
 
+// complex column x of a row: cpx_cols[x] when the caller gave the per-column
+// array, else the legacy single-column fields stand for column 0
+static gpuc_cpx_col cpx_col_of(const gpuc_unfiltered& U, uint32_t x) {
+    if (U.cpx_cols) return U.cpx_cols[x];
+    if (x == 0 && U.has_cpx)
+        return gpuc_cpx_col{1, U.cpx_del_mfda, U.cpx_del_ldt, U.n_cpx_cells, U.cpx_cells};
+    return gpuc_cpx_col{0, INT64_MIN, LDT_NONE_U32, 0, nullptr};
+}
+// CellPath order of map<blob,blob> keys: unsigned bytes, shorter first
+static int h_path_cmp(const gpuc_cpx_cell& a, const gpuc_cpx_cell& b) {
+    uint32_t n = a.path_len < b.path_len ? a.path_len : b.path_len;
+    int c = n ? memcmp(a.path, b.path, n) : 0;
+    if (c) return c;
+    return a.path_len == b.path_len ? 0 : (a.path_len < b.path_len ? -1 : 1);
+}
+
 }  // namespace flushv2
 
 extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flush_part* parts,
@@ -3126,7 +3167,7 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         (void)checked_chunk_len_arg(S.chunk_length, CHUNK_LEN);  // before any work
         if (S.n_cols == 0 || S.n_cols + S.n_static > 63)
             throw std::runtime_error("1..63 columns supported");
-        if (S.n_cpx > 1) throw std::runtime_error("at most one complex column");
+        if (S.n_cpx > S.n_cols) throw std::runtime_error("n_cpx exceeds n_cols");
         if (S.n_ck > 32) throw std::runtime_error("at most 32 clustering columns");
         const std::string MAPT_PFX = "org.apache.cassandra.db.marshal.MapType";
         const std::string CTRT = "org.apache.cassandra.db.marshal.CounterColumnType";
@@ -3139,16 +3180,18 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
             ckw_h.push_back(ck_type_width(ck_types.back()));
         }
         // n_cols in the ABI counts ALL regular columns; SchemaParams.n_cols
-        // counts the SIMPLE ones (complex last, excluded)
+        // counts the SIMPLE ones (the n_cpx complex ones last, excluded)
         const uint32_t NSIMPLE = S.n_cols - S.n_cpx;
+        const uint32_t NX = S.n_cpx;
         std::vector<std::pair<bytes, std::string>> regular_cols, static_cols;
         std::vector<int32_t> colw_h, staticw_h;
         bool counters = false;
         for (uint32_t i = 0; i < S.n_cols; i++) {
             std::string t(S.col_types[i]);
             bool is_map = t.compare(0, MAPT_PFX.size(), MAPT_PFX) == 0;
-            if (is_map != (S.n_cpx == 1 && i == S.n_cols - 1))
-                throw std::runtime_error("a complex (MapType) column must be the last regular column");
+            if (is_map != (i >= NSIMPLE))
+                throw std::runtime_error(
+                    "the complex (MapType) columns must be the last n_cpx regular columns");
             if (t == CTRT) counters = true;
             regular_cols.emplace_back(bytes(S.col_names[i], S.col_names[i] + S.col_name_lens[i]), t);
             if (i < NSIMPLE)
@@ -3189,12 +3232,24 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                 if (is_row) {
                     for (uint32_t c = 0; c < NSIMPLE; c++)
                         if (U.cells[c].flags & GPUC_CELLF_PRESENT) val_bytes += U.cells[c].value_len;
-                    if (U.has_cpx && !S.n_cpx)
+                    if ((U.has_cpx || U.cpx_cols) && !S.n_cpx)
                         throw std::runtime_error("complex data on a schema without a complex column");
-                    if (U.has_cpx) {
-                        cpx_total += U.n_cpx_cells;
-                        for (uint32_t e = 0; e < U.n_cpx_cells; e++)
-                            val_bytes += U.cpx_cells[e].path_len + U.cpx_cells[e].cell.value_len;
+                    if (S.n_cpx >= 2 && U.has_cpx && !U.cpx_cols)
+                        throw std::runtime_error(
+                            "a row with complex data needs cpx_cols when the schema has "
+                            "several complex columns");
+                    for (uint32_t x = 0; x < S.n_cpx; x++) {
+                        const gpuc_cpx_col X = cpx_col_of(U, x);
+                        if (!X.present) continue;
+                        cpx_total += X.n_cells;
+                        for (uint32_t e = 0; e < X.n_cells; e++) {
+                            const gpuc_cpx_cell& C = X.cells[e];
+                            val_bytes += C.path_len + C.cell.value_len;
+                            if (e && h_path_cmp(X.cells[e - 1], C) >= 0)
+                                throw std::runtime_error(
+                                    "complex cells out of CellPath order in partition " +
+                                    std::to_string(p) + ", complex column " + std::to_string(x));
+                        }
                     }
                 }
                 if (prev && h_unf_cmp(*prev, U, ckw_h) >= 0)
@@ -3292,9 +3347,11 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         std::vector<uint32_t> h_rdl(n_unf, LDT_NONE_U32), h_sl(n_unf, LDT_NONE_U32),
             h_cldt(n_unf * NCV, 0), h_cvl(n_unf * NCV, 0);
         std::vector<uint64_t> h_cva(n_unf * NCV, 0);
-        std::vector<int64_t> h_xdm(S.n_cpx ? n_unf : 0);
-        std::vector<uint32_t> h_xdl(S.n_cpx ? n_unf : 0), h_xcnt(S.n_cpx ? n_unf : 0);
-        std::vector<uint64_t> h_xstart(S.n_cpx ? n_unf : 0);
+        // per (unfiltered, complex column), strided by NX
+        std::vector<uint8_t> h_xp(n_unf * NX, 0);
+        std::vector<int64_t> h_xdm(n_unf * NX, INT64_MIN);
+        std::vector<uint32_t> h_xdl(n_unf * NX, LDT_NONE_U32), h_xcnt(n_unf * NX, 0);
+        std::vector<uint64_t> h_xstart(n_unf * NX, 0);
         std::vector<int64_t> h_xts(cpx_total);
         std::vector<uint32_t> h_xldt(cpx_total), h_xpl(cpx_total), h_xvl(cpx_total);
         std::vector<int32_t> h_xttl(cpx_total);
@@ -3372,23 +3429,23 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                         conv_cell(U.cells[c], &h_cts[ob * NCV + c], &h_cldt[ob * NCV + c],
                                   &h_cttl[ob * NCV + c], &h_cva[ob * NCV + c],
                                   &h_cvl[ob * NCV + c], &h_cf[ob * NCV + c]);
-                    if (S.n_cpx) {
-                        h_xdm[ob] = INT64_MIN;
-                        h_xdl[ob] = LDT_NONE_U32;
-                        h_xstart[ob] = xcur;
-                        h_xcnt[ob] = 0;
-                        if (U.has_cpx) {
-                            f |= PF_HAS_CPX;
-                            h_xdm[ob] = U.cpx_del_mfda;
-                            h_xdl[ob] = U.cpx_del_ldt;
-                            h_xcnt[ob] = U.n_cpx_cells;
-                            for (uint32_t e = 0; e < U.n_cpx_cells; e++, xcur++) {
-                                const gpuc_cpx_cell& X = U.cpx_cells[e];
-                                conv_cell(X.cell, &h_xts[xcur], &h_xldt[xcur], &h_xttl[xcur],
-                                          &h_xva[xcur], &h_xvl[xcur], &h_xf[xcur]);
-                                h_xpa[xcur] = stash(X.path, X.path_len);
-                                h_xpl[xcur] = X.path_len;
-                            }
+                    // a row's segments lie end to end in header order
+                    for (uint32_t x = 0; x < NX; x++) {
+                        const uint64_t ox = ob * NX + x;
+                        const gpuc_cpx_col X = cpx_col_of(U, x);
+                        h_xstart[ox] = xcur;
+                        if (!X.present) continue;
+                        f |= PF_HAS_CPX;
+                        h_xp[ox] = 1;
+                        h_xdm[ox] = X.del_mfda;
+                        h_xdl[ox] = X.del_ldt;
+                        h_xcnt[ox] = X.n_cells;
+                        for (uint32_t e = 0; e < X.n_cells; e++, xcur++) {
+                            const gpuc_cpx_cell& C = X.cells[e];
+                            conv_cell(C.cell, &h_xts[xcur], &h_xldt[xcur], &h_xttl[xcur],
+                                      &h_xva[xcur], &h_xvl[xcur], &h_xf[xcur]);
+                            h_xpa[xcur] = stash(C.path, C.path_len);
+                            h_xpl[xcur] = C.path_len;
                         }
                     }
                     h_flags[ob] = f;
@@ -3400,12 +3457,7 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                         h_sm[ob] = U.open_mfda;
                         h_sl[ob] = U.open_ldt;
                     }
-                    if (S.n_cpx) {
-                        h_xdm[ob] = INT64_MIN;
-                        h_xdl[ob] = LDT_NONE_U32;
-                        h_xstart[ob] = xcur;
-                        h_xcnt[ob] = 0;
-                    }
+                    for (uint32_t x = 0; x < NX; x++) h_xstart[ob * NX + x] = xcur;
                 }
             }
         }
@@ -3457,10 +3509,11 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         up(urows.val_len, h_cvl.data(), n_unf * NCV * 4);
         up(urows.cell_flags, h_cf.data(), n_unf * NCV);
         if (S.n_cpx) {
-            up(urows.cpx_del_mfda, h_xdm.data(), n_unf * 8);
-            up(urows.cpx_del_ldt, h_xdl.data(), n_unf * 4);
-            up(urows.cpx_start, h_xstart.data(), n_unf * 8);
-            up(urows.cpx_count, h_xcnt.data(), n_unf * 4);
+            up(urows.cpx_present, h_xp.data(), n_unf * NX);
+            up(urows.cpx_del_mfda, h_xdm.data(), n_unf * NX * 8);
+            up(urows.cpx_del_ldt, h_xdl.data(), n_unf * NX * 4);
+            up(urows.cpx_start, h_xstart.data(), n_unf * NX * 8);
+            up(urows.cpx_count, h_xcnt.data(), n_unf * NX * 4);
             if (cpx_total) {
                 up(urows.cx_ts, h_xts.data(), cpx_total * 8);
                 up(urows.cx_ldt, h_xldt.data(), cpx_total * 4);
@@ -3483,7 +3536,8 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         d_tomb.alloc((uint64_t)tomb_cap * 4);
         uint32_t blocks = (uint32_t)((n_parts + 255) / 256);
         hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op, urows.uc,
-                           n_parts, NCV, d_stats.as<OutStats>(), d_tomb.as<uint32_t>(), tomb_cap);
+                           n_parts, NCV, NX, d_stats.as<OutStats>(), d_tomb.as<uint32_t>(),
+                           tomb_cap);
         OutStats hs0;
         HIP_CHECK(hipStreamSynchronize(stream));
         HIP_CHECK(hipMemcpy(&hs0, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
@@ -3664,7 +3718,8 @@ extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* e
             d_tomb.alloc((uint64_t)tomb_cap * 4);
             {
                 hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op,
-                                   rows.uc, R, gp.n_value_cols, d_stats.as<OutStats>(),
+                                   rows.uc, R, gp.n_value_cols, gp.complex_pct ? 1u : 0u,
+                                   d_stats.as<OutStats>(),
                                    d_tomb.as<uint32_t>(), tomb_cap);
             }
             OutStats hs0;

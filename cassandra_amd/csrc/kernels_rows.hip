@@ -30,8 +30,9 @@ struct SchemaParams {
     const int32_t* ck_w;     // per clustering column: 4/8 fixed or -1 variable
     uint32_t n_cols;         // SIMPLE regular columns (1..63; header order)
     const int32_t* col_fixed;  // per simple column: -1 variable else fixed width
-    uint32_t n_cpx;          // 0 or 1: one complex column AFTER the simple ones
-                             // (subset bitmap covers n_cols + n_cpx bits)
+    uint32_t n_cpx;          // complex columns, all AFTER the simple ones (subset
+                             // bitmap bit n_cols + x is complex column x;
+                             // n_cols + n_cpx <= 63)
     uint32_t n_static;       // static columns (0 = schema has no statics)
     const int32_t* static_fixed;
     uint32_t column_index_size;  // promoted-index granularity (64 KiB default)
@@ -339,11 +340,13 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
             rc.live_ttl[o] = 0;
             rc.live_let[o] = NO_DELETION_TIME;
             for (uint32_t c = 0; c < sp.n_cols; c++) rc.cell_flags[o * sp.n_cols + c] = 0;
-            if (sp.n_cpx) {
-                rc.cpx_del_mfda[o] = INT64_MIN;
-                rc.cpx_del_ldt[o] = LDT_NONE_U32;
-                rc.cpx_start[o] = cpx_cur;
-                rc.cpx_count[o] = 0;
+            for (uint32_t x = 0; x < sp.n_cpx; x++) {
+                uint64_t ox = o * sp.n_cpx + x;
+                rc.cpx_present[ox] = 0;
+                rc.cpx_del_mfda[ox] = INT64_MIN;
+                rc.cpx_del_ldt[ox] = LDT_NONE_U32;
+                rc.cpx_start[ox] = cpx_cur;
+                rc.cpx_count[ox] = 0;
             }
         } else {
             // ---- row ----
@@ -413,20 +416,26 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
                 rc.val_addr[oc] = vaddr;
                 rc.val_len[oc] = vlen;
             }
-            // ---- complex column (bit sp.n_cols of the subset bitmap) ----
-            if (sp.n_cpx) {
-                rc.cpx_del_mfda[o] = INT64_MIN;
-                rc.cpx_del_ldt[o] = LDT_NONE_U32;
-                rc.cpx_count[o] = 0;
-                rc.cpx_start[o] = cpx_cur;
-                if (!(missing & (1ULL << sp.n_cols))) {
+            // ---- complex columns (bit sp.n_cols + x of the subset bitmap) ----
+            for (uint32_t x = 0; x < sp.n_cpx; x++) {
+                uint64_t ox = o * sp.n_cpx + x;
+                bool xp = !(missing & (1ULL << (sp.n_cols + x)));
+                rc.cpx_present[ox] = xp;
+                rc.cpx_del_mfda[ox] = INT64_MIN;
+                rc.cpx_del_ldt[ox] = LDT_NONE_U32;
+                rc.cpx_count[ox] = 0;
+                rc.cpx_start[ox] = cpx_cur;
+                if (xp) {
                     pf |= PF_HAS_CPX;
-                    if (flags & 0x40) {  // HAS_COMPLEX_DELETION: per-column deletion
-                        rc.cpx_del_mfda[o] = (int64_t)uvint_get(base, &pos) + sd.min_ts;
-                        rc.cpx_del_ldt[o] = ldt_u32((int64_t)(int32_t)(uint32_t)uvint_get(base, &pos) + sd.min_ldt);
+                    if (flags & 0x40) {
+                        // HAS_COMPLEX_DELETION: EVERY present column carries a
+                        // deletion; DeletionTime.LIVE comes back through the
+                        // delta codec as (INT64_MIN, -1 -> LDT_NONE_U32)
+                        rc.cpx_del_mfda[ox] = (int64_t)(uvint_get(base, &pos) + (uint64_t)sd.min_ts);
+                        rc.cpx_del_ldt[ox] = ldt_u32((int64_t)(int32_t)(uint32_t)uvint_get(base, &pos) + sd.min_ldt);
                     }
                     uint32_t ncc = (uint32_t)uvint_get(base, &pos);
-                    rc.cpx_count[o] = ncc;
+                    rc.cpx_count[ox] = ncc;
                     for (uint32_t e = 0; e < ncc; e++) {
                         uint8_t cf = base[pos++];
                         int64_t cts = (cf & 8) ? lts : (int64_t)uvint_get(base, &pos) + sd.min_ts;
@@ -638,11 +647,13 @@ __global__ void k_validate_digest(OutParts op, UnfCols out, uint64_t n, Validate
                                 (const uint8_t*)out.val_addr[oc], out.val_len[oc],
                                 vp.counters && out.cell_ldt[oc] == LDT_NONE_U32, nullptr, 0);
             }
-            if (vp.n_cpx && (f & PF_HAS_CPX)) {
-                bool del_live = out.cpx_del_mfda[o] == INT64_MIN && out.cpx_del_ldt[o] == LDT_NONE_U32;
-                if (!del_live) i64(out.cpx_del_mfda[o]);
-                uint64_t si = out.cpx_start[o];
-                for (uint32_t e = 0; e < out.cpx_count[o]; e++) {
+            for (uint32_t x = 0; x < vp.n_cpx && (f & PF_HAS_CPX); x++) {
+                uint64_t ox = o * vp.n_cpx + x;
+                if (!out.cpx_present[ox]) continue;
+                bool del_live = out.cpx_del_mfda[ox] == INT64_MIN && out.cpx_del_ldt[ox] == LDT_NONE_U32;
+                if (!del_live) i64(out.cpx_del_mfda[ox]);
+                uint64_t si = out.cpx_start[ox];
+                for (uint32_t e = 0; e < out.cpx_count[ox]; e++) {
                     uint64_t xe = si + e;
                     put_cell_fields(out.cpx.ts[xe], out.cpx.ttl[xe],
                                     (const uint8_t*)out.cpx.val_addr[xe], out.cpx.val_len[xe],
@@ -1198,11 +1209,10 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
             const uint32_t NC = sp.n_cols;
             uint64_t oslot = obase + ocount;  // cells written here pre-emit
             bool any_cell = false;
-            // merged complex column (ColumnDataReducer complex branch)
-            int64_t xdm = INT64_MIN;
-            uint32_t xdl = LDT_NONE_U32;
-            uint64_t xstart = 0;
-            uint32_t xcnt = 0;
+            // merged complex columns (ColumnDataReducer complex branch) go
+            // straight to the out slot, one column at a time; the row takes
+            // ONE arena allocation and lays its columns' segments end to end
+            const uint32_t NX = sp.n_cpx;
             if (k == 1 || (nmem == 1 && active_live)) {
                 uint64_t o = last_o;
                 of = in.flags[o];
@@ -1220,23 +1230,32 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                     out.val_addr[ocx] = in.val_addr[ic];
                     out.val_len[ocx] = in.val_len[ic];
                 }
-                if (sp.n_cpx && (of & PF_HAS_CPX)) {
-                    xdm = in.cpx_del_mfda[o];
-                    xdl = in.cpx_del_ldt[o];
-                    uint32_t nc2 = in.cpx_count[o];
-                    xstart = atomicAdd(&st->cpx_alloc, (unsigned long long)nc2);
-                    uint64_t si = in.cpx_start[o];
-                    for (uint32_t e2 = 0; e2 < nc2; e2++) {
-                        out.cpx.ts[xstart + e2] = in.cpx.ts[si + e2];
-                        out.cpx.ldt[xstart + e2] = in.cpx.ldt[si + e2];
-                        out.cpx.ttl[xstart + e2] = in.cpx.ttl[si + e2];
-                        out.cpx.flags[xstart + e2] = in.cpx.flags[si + e2];
-                        out.cpx.path_addr[xstart + e2] = in.cpx.path_addr[si + e2];
-                        out.cpx.path_len[xstart + e2] = in.cpx.path_len[si + e2];
-                        out.cpx.val_addr[xstart + e2] = in.cpx.val_addr[si + e2];
-                        out.cpx.val_len[xstart + e2] = in.cpx.val_len[si + e2];
+                if (NX && (of & PF_HAS_CPX)) {
+                    // (absent columns hold count 0)
+                    uint32_t totc = 0;
+                    for (uint32_t x = 0; x < NX; x++) totc += in.cpx_count[o * NX + x];
+                    uint64_t xcur = atomicAdd(&st->cpx_alloc, (unsigned long long)totc);
+                    for (uint32_t x = 0; x < NX; x++) {
+                        uint64_t ix = o * NX + x, oxx = oslot * NX + x;
+                        uint32_t nc2 = in.cpx_count[ix];
+                        uint64_t si = in.cpx_start[ix];
+                        for (uint32_t e2 = 0; e2 < nc2; e2++) {
+                            out.cpx.ts[xcur + e2] = in.cpx.ts[si + e2];
+                            out.cpx.ldt[xcur + e2] = in.cpx.ldt[si + e2];
+                            out.cpx.ttl[xcur + e2] = in.cpx.ttl[si + e2];
+                            out.cpx.flags[xcur + e2] = in.cpx.flags[si + e2];
+                            out.cpx.path_addr[xcur + e2] = in.cpx.path_addr[si + e2];
+                            out.cpx.path_len[xcur + e2] = in.cpx.path_len[si + e2];
+                            out.cpx.val_addr[xcur + e2] = in.cpx.val_addr[si + e2];
+                            out.cpx.val_len[xcur + e2] = in.cpx.val_len[si + e2];
+                        }
+                        out.cpx_present[oxx] = in.cpx_present[ix];
+                        out.cpx_del_mfda[oxx] = in.cpx_del_mfda[ix];
+                        out.cpx_del_ldt[oxx] = in.cpx_del_ldt[ix];
+                        out.cpx_start[oxx] = xcur;
+                        out.cpx_count[oxx] = nc2;
+                        xcur += nc2;
                     }
-                    xcnt = nc2;
                 }
             } else {
                 bool has_live = false;
@@ -1480,11 +1499,11 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                         out.cell_flags[ocx] = 0;
                     }
                 }
-                if (sp.n_cpx) {
-                    // complexDeletion = max over versions; supersedes(active)
-                    // decides both the cell filter and whether it is kept
-                    // (Row.java:857-874)
-                    bool anyv = false;
+                // the row's arena allocation: every member's cells over all
+                // columns (an upper bound on what the merge keeps)
+                bool anyv = false;
+                uint32_t totc = 0;
+                if (NX) {
                     #pragma unroll
         for (uint32_t m = 0; m < (uint32_t)MA; m++) {
             if (m >= k) break;
@@ -1492,12 +1511,32 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                         uint64_t o = mb[m] + mpos[m];
                         if (!(in.flags[o] & PF_HAS_CPX)) continue;
                         anyv = true;
-                        if (dt_sup(in.cpx_del_mfda[o], in.cpx_del_ldt[o], xdm, xdl)) {
-                            xdm = in.cpx_del_mfda[o];
-                            xdl = in.cpx_del_ldt[o];
+                        for (uint32_t x = 0; x < NX; x++) totc += in.cpx_count[o * NX + x];
+                    }
+                }
+                uint64_t xcur = anyv ? atomicAdd(&st->cpx_alloc, (unsigned long long)totc) : 0;
+                for (uint32_t x = 0; x < NX && anyv; x++) {
+                    // complexDeletion = max over versions; supersedes(active)
+                    // decides both the cell filter and whether it is kept
+                    // (Row.java:857-874)
+                    const uint64_t oxx = oslot * NX + x;
+                    int64_t xdm = INT64_MIN;
+                    uint32_t xdl = LDT_NONE_U32;
+                    uint32_t xcnt = 0;
+                    bool anyx = false;
+                    #pragma unroll
+        for (uint32_t m = 0; m < (uint32_t)MA; m++) {
+            if (m >= k) break;
+                        if (!(members & (1ULL << m))) continue;
+                        uint64_t o = mb[m] + mpos[m];
+                        if (!(in.flags[o] & PF_HAS_CPX) || !in.cpx_present[o * NX + x]) continue;
+                        anyx = true;
+                        if (dt_sup(in.cpx_del_mfda[o * NX + x], in.cpx_del_ldt[o * NX + x], xdm, xdl)) {
+                            xdm = in.cpx_del_mfda[o * NX + x];
+                            xdl = in.cpx_del_ldt[o * NX + x];
                         }
                     }
-                    if (anyv) {
+                    if (anyx) {
                         int64_t cam = am2;
                         uint32_t cal = al2;
                         bool keep_del = dt_sup(xdm, xdl, am2, al2);
@@ -1505,20 +1544,19 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                         else { xdm = INT64_MIN; xdl = LDT_NONE_U32; }
                         uint32_t ppos[MA], pcnt[MA];
                         uint64_t pbase[MA];
-                        uint32_t nv2 = 0, totc = 0;
+                        uint32_t nv2 = 0;
                         #pragma unroll
         for (uint32_t m = 0; m < (uint32_t)MA; m++) {
             if (m >= k) break;
                             if (!(members & (1ULL << m))) continue;
                             uint64_t o = mb[m] + mpos[m];
-                            if (!(in.flags[o] & PF_HAS_CPX)) continue;
-                            pbase[nv2] = in.cpx_start[o];
-                            pcnt[nv2] = in.cpx_count[o];
+                            if (!(in.flags[o] & PF_HAS_CPX) || !in.cpx_present[o * NX + x]) continue;
+                            pbase[nv2] = in.cpx_start[o * NX + x];
+                            pcnt[nv2] = in.cpx_count[o * NX + x];
                             ppos[nv2] = 0;
-                            totc += in.cpx_count[o];
                             nv2++;
                         }
-                        xstart = atomicAdd(&st->cpx_alloc, (unsigned long long)totc);
+                        const uint64_t xstart = xcur;
                         auto cmp_path = [&](uint64_t a, uint64_t b) -> int {
                             return cmp_values(in.cpx.path_addr[a], in.cpx.path_len[a],
                                               in.cpx.path_addr[b], in.cpx.path_len[b]);
@@ -1596,12 +1634,19 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                                 out.cpx.val_len[xe2] = vl;
                             }
                         }
-                        // Builder.build: live deletion + no cells -> null column
-                        if (xcnt || xdm != INT64_MIN || xdl != LDT_NONE_U32) {
-                            of |= PF_HAS_CPX;
-                            any_cell = true;
-                        }
                     }
+                    // Builder.build: live deletion + no cells -> null column
+                    bool xp = xcnt || xdm != INT64_MIN || xdl != LDT_NONE_U32;
+                    if (xp) {
+                        of |= PF_HAS_CPX;
+                        any_cell = true;
+                    }
+                    out.cpx_present[oxx] = xp;
+                    out.cpx_del_mfda[oxx] = xdm;
+                    out.cpx_del_ldt[oxx] = xdl;
+                    out.cpx_start[oxx] = xcur;
+                    out.cpx_count[oxx] = xcnt;
+                    xcur += xcnt;
                 }
                 if ((of & (PF_LIVE_TS | PF_ROW_DEL)) || any_cell) of |= PF_HAS_ROW;
                 else of = 0;
@@ -1635,8 +1680,15 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                     }
                     any_cell = true;
                 }
-                if (sp.n_cpx && (of & PF_HAS_CPX)) {
+                bool any_cpx = false;
+                for (uint32_t x = 0; x < NX && (of & PF_HAS_CPX); x++) {
+                    const uint64_t oxx = oslot * NX + x;
+                    if (!out.cpx_present[oxx]) continue;
                     // ComplexColumnData.purge (ComplexColumnData.java:212-216)
+                    int64_t xdm = out.cpx_del_mfda[oxx];
+                    uint32_t xdl = out.cpx_del_ldt[oxx];
+                    const uint64_t xstart = out.cpx_start[oxx];
+                    uint32_t xcnt = out.cpx_count[oxx];
                     if (xdm != INT64_MIN && should_purge2(pp, token, xdm, ldt_long(xdl))) {
                         xdm = INT64_MIN;
                         xdl = LDT_NONE_U32;
@@ -1672,19 +1724,19 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                         out.cpx.val_len[xo] = vl;
                     }
                     xcnt = w;
-                    if (xcnt == 0 && xdm == INT64_MIN && xdl == LDT_NONE_U32) of &= ~PF_HAS_CPX;
-                    else any_cell = true;
+                    bool xp = xcnt || xdm != INT64_MIN || xdl != LDT_NONE_U32;
+                    out.cpx_present[oxx] = xp;
+                    out.cpx_del_mfda[oxx] = xdm;
+                    out.cpx_del_ldt[oxx] = xdl;
+                    out.cpx_count[oxx] = xcnt;
+                    any_cpx |= xp;
                 }
+                if (any_cpx) any_cell = true;
+                else of &= ~PF_HAS_CPX;
                 if (!(of & (PF_LIVE_TS | PF_ROW_DEL)) && !any_cell) of = 0;
                 else if (pp.enforce_strict_liveness && !(of & PF_LIVE_TS) && !(of & PF_ROW_DEL)) of = 0;
             }
             if (of & PF_HAS_ROW) {
-                if (sp.n_cpx) {
-                    out.cpx_del_mfda[oslot] = xdm;
-                    out.cpx_del_ldt[oslot] = xdl;
-                    out.cpx_start[oslot] = xstart;
-                    out.cpx_count[oslot] = (of & PF_HAS_CPX) ? xcnt : 0;
-                }
                 emit(BK_CLUSTERING, fck, of, lts, lttl, llet, rdm, rdl, INT64_MIN, LDT_NONE_U32,
                      true);
             }
@@ -1901,31 +1953,40 @@ __device__ inline uint32_t unf_body_size(const UnfCols& u, uint64_t o, const Ser
     // the superset covers simple columns + the complex column (bit n_cols)
     uint64_t present_mask = 0;
     uint32_t present = 0;
-    const uint32_t NSUP = sp.sch.n_cols + sp.sch.n_cpx;
-    bool has_cpx = sp.sch.n_cpx && (f & PF_HAS_CPX);
-    for (uint32_t c = 0; c < sp.sch.n_cols; c++)
-        if (u.cell_flags[o * sp.sch.n_cols + c] & CELLF_PRESENT) { present_mask |= 1ULL << c; present++; }
-    if (has_cpx) { present_mask |= 1ULL << sp.sch.n_cols; present++; }
-    if (present == NSUP) rflags |= 0x20;
-    else body += uvint_size(((1ULL << NSUP) - 1) & ~present_mask);
+    const uint32_t NX = sp.sch.n_cpx;
+    const uint32_t NSUP = sp.sch.n_cols + NX;
     for (uint32_t c = 0; c < sp.sch.n_cols; c++) {
         uint64_t oc = o * sp.sch.n_cols + c;
         if (!(u.cell_flags[oc] & CELLF_PRESENT)) continue;
+        present_mask |= 1ULL << c;
+        present++;
         uint8_t cflags;
         body += cell_body_size(u, oc, sp, sp.sch.col_fixed[c], live, exp_live, o, &cflags);
     }
-    if (has_cpx) {
-        bool del_live = u.cpx_del_mfda[o] == INT64_MIN && u.cpx_del_ldt[o] == LDT_NONE_U32;
-        if (!del_live) rflags |= 0x40;  // HAS_COMPLEX_DELETION
-        if (rflags & 0x40)
-            body += uvint_size((uint64_t)(u.cpx_del_mfda[o] - sp.hs.min_ts)) +
-                    uvint_size(sext32(ldt_long(u.cpx_del_ldt[o]) - sp.hs.min_ldt));
-        uint32_t nc2 = u.cpx_count[o];
-        body += uvint_size(nc2);
-        uint64_t si = u.cpx_start[o];
-        for (uint32_t e2 = 0; e2 < nc2; e2++)
-            body += cpx_cell_body_size(u, si + e2, sp, live, exp_live, o, nullptr);
+    if (NX && (f & PF_HAS_CPX)) {
+        // HAS_COMPLEX_DELETION iff ANY present complex column has a non-live
+        // deletion; then EVERY present column writes its own (a live one
+        // too, as (INT64_MIN, NO_DELETION_TIME) through the delta codec)
+        uint32_t del_sz = 0;
+        bool any_del = false;
+        for (uint32_t x = 0; x < NX; x++) {
+            const uint64_t ox = o * NX + x;
+            if (!u.cpx_present[ox]) continue;
+            present_mask |= 1ULL << (sp.sch.n_cols + x);
+            present++;
+            any_del |= u.cpx_del_mfda[ox] != INT64_MIN || u.cpx_del_ldt[ox] != LDT_NONE_U32;
+            del_sz += uvint_size((uint64_t)u.cpx_del_mfda[ox] - (uint64_t)sp.hs.min_ts) +
+                      uvint_size(sext32(ldt_long(u.cpx_del_ldt[ox]) - sp.hs.min_ldt));
+            uint32_t nc2 = u.cpx_count[ox];
+            body += uvint_size(nc2);
+            uint64_t si = u.cpx_start[ox];
+            for (uint32_t e2 = 0; e2 < nc2; e2++)
+                body += cpx_cell_body_size(u, si + e2, sp, live, exp_live, o, nullptr);
+        }
+        if (any_del) { rflags |= 0x40; body += del_sz; }
     }
+    if (present == NSUP) rflags |= 0x20;
+    else body += uvint_size(((1ULL << NSUP) - 1) & ~present_mask);
     if (out_flags) *out_flags = rflags;
     if (out_cflags) *out_cflags = 0;
     return body;
@@ -2264,7 +2325,10 @@ __device__ uint64_t part_walk(const OutParts& op, const UnfCols& out, uint64_t g
                 const uint32_t NSUP = sp.sch.n_cols + sp.sch.n_cpx;
                 for (uint32_t c = 0; c < sp.sch.n_cols; c++)
                     if (out.cell_flags[o * sp.sch.n_cols + c] & CELLF_PRESENT) present_mask |= 1ULL << c;
-                if (sp.sch.n_cpx && (out.flags[o] & PF_HAS_CPX)) present_mask |= 1ULL << sp.sch.n_cols;
+                if (sp.sch.n_cpx && (out.flags[o] & PF_HAS_CPX))
+                    for (uint32_t x = 0; x < sp.sch.n_cpx; x++)
+                        if (out.cpx_present[o * sp.sch.n_cpx + x])
+                            present_mask |= 1ULL << (sp.sch.n_cols + x);
                 emit_uv(((1ULL << NSUP) - 1) & ~present_mask);
             }
             bool live = rflags & 0x04, exp_live = rflags & 0x08;
@@ -2288,15 +2352,17 @@ __device__ uint64_t part_walk(const OutParts& op, const UnfCols& out, uint64_t g
                     pos += vlen;
                 }
             }
-            // ---- complex column (UnfilteredSerializer.writeComplexColumn) ----
-            if (sp.sch.n_cpx && (out.flags[o] & PF_HAS_CPX)) {
+            // ---- complex columns (UnfilteredSerializer.writeComplexColumn) ----
+            for (uint32_t x = 0; x < ((out.flags[o] & PF_HAS_CPX) ? sp.sch.n_cpx : 0u); x++) {
+                const uint64_t ox = o * sp.sch.n_cpx + x;
+                if (!out.cpx_present[ox]) continue;
                 if (rflags & 0x40) {
-                    emit_uv((uint64_t)(out.cpx_del_mfda[o] - sp.hs.min_ts));
-                    emit_uv(sext32(ldt_long(out.cpx_del_ldt[o]) - sp.hs.min_ldt));
+                    emit_uv((uint64_t)out.cpx_del_mfda[ox] - (uint64_t)sp.hs.min_ts);
+                    emit_uv(sext32(ldt_long(out.cpx_del_ldt[ox]) - sp.hs.min_ldt));
                 }
-                uint32_t nc2 = out.cpx_count[o];
+                uint32_t nc2 = out.cpx_count[ox];
                 emit_uv(nc2);
-                uint64_t si = out.cpx_start[o];
+                uint64_t si = out.cpx_start[ox];
                 for (uint32_t e2 = 0; e2 < nc2; e2++) {
                     uint64_t xe = si + e2;
                     uint8_t cfb;
@@ -2428,7 +2494,8 @@ __global__ void k_sizes_rows(OutParts op, UnfCols out, uint64_t n, SerParams2 sp
                 uint64_t ro = op.row_base[g] + j;
                 for (uint32_t c = 0; c < sp.sch.n_cols; c++)
                     if (out.cell_flags[ro * sp.sch.n_cols + c] & CELLF_PRESENT) cells++;
-                if (sp.sch.n_cpx && (out.flags[ro] & PF_HAS_CPX)) cells += out.cpx_count[ro];
+                for (uint32_t x = 0; x < sp.sch.n_cpx && (out.flags[ro] & PF_HAS_CPX); x++)
+                    if (out.cpx_present[ro * sp.sch.n_cpx + x]) cells += out.cpx_count[ro * sp.sch.n_cpx + x];
             }
             lo = 0; hi = ch_hist_n;
             while (lo < hi) { int mid = (lo + hi) >> 1; if ((uint64_t)ch_hist_off[mid] < cells) lo = mid + 1; else hi = mid; }
@@ -2497,7 +2564,8 @@ __global__ void k_serialize_rows(OutParts op, UnfCols out, uint64_t n, SerParams
 }
 
 // output stats over the final OutParts/UnfCols (MetadataCollector semantics)
-__global__ void k_collect_rows(OutParts op, UnfCols out, uint64_t n, uint32_t n_cols, OutStats* st,
+__global__ void k_collect_rows(OutParts op, UnfCols out, uint64_t n, uint32_t n_cols,
+                               uint32_t n_cpx, OutStats* st,
                                uint32_t* tomb_ldts, uint32_t tomb_cap) {
     __shared__ unsigned long long sh_parts, sh_rows, sh_cells, sh_mints, sh_maxts,
         sh_minldt, sh_maxldt, sh_haspdel;
@@ -2575,20 +2643,22 @@ __global__ void k_collect_rows(OutParts op, UnfCols out, uint64_t n, uint32_t n_
                     atomicMax(&sh_maxttl, (unsigned)cttl);
                 } else lldt(NO_DELETION_TIME);
             }
-            if (of & PF_HAS_CPX) {
+            for (uint32_t x = 0; x < n_cpx && (of & PF_HAS_CPX); x++) {
                 // MetadataCollector.update(complexDeletion) + per-cell stats;
-                // totalColumnsSet counts the COLUMN once when it has cells
+                // totalColumnsSet counts each COLUMN once when it has cells
                 // (Rows.java:66-82)
-                int64_t xdm = out.cpx_del_mfda[o];
-                uint32_t xdl = out.cpx_del_ldt[o];
+                const uint64_t ox = o * n_cpx + x;
+                if (!out.cpx_present[ox]) continue;
+                int64_t xdm = out.cpx_del_mfda[ox];
+                uint32_t xdl = out.cpx_del_ldt[ox];
                 if (!(xdm == INT64_MIN && xdl == LDT_NONE_U32)) {
                     lts(xdm);
                     lldt(ldt_long(xdl));
                     tomb_push(st, tomb_ldts, tomb_cap, xdl);
                 }
-                uint32_t nc2 = out.cpx_count[o];
+                uint32_t nc2 = out.cpx_count[ox];
                 if (nc2) atomicAdd(&sh_cells, 1ull);
-                uint64_t si = out.cpx_start[o];
+                uint64_t si = out.cpx_start[ox];
                 for (uint32_t e2 = 0; e2 < nc2; e2++) {
                     uint64_t xe = si + e2;
                     lts(out.cpx.ts[xe]);
@@ -2821,27 +2891,32 @@ __device__ inline bool gc_row_filter_active(UnfCols& out, uint64_t o, int64_t am
             if (out.cell_ts[oc] <= am) out.cell_flags[oc] = 0;
             else any_cell = true;
         }
-        if (sch.n_cpx && (f & PF_HAS_CPX)) {
+        bool any_cpx = false;
+        for (uint32_t x = 0; x < sch.n_cpx && (f & PF_HAS_CPX); x++) {
             // ComplexColumnData.filter(all, activeDeletion, null, -)
             // (ComplexColumnData.java:188-210): drop a shadowed
             // complexDeletion, drop cells activeDeletion deletes
-            if (dtp_sup(am, al, out.cpx_del_mfda[o], out.cpx_del_ldt[o])) {
-                out.cpx_del_mfda[o] = INT64_MIN;
-                out.cpx_del_ldt[o] = LDT_NONE_U32;
+            const uint64_t ox = o * sch.n_cpx + x;
+            if (!out.cpx_present[ox]) continue;
+            if (dtp_sup(am, al, out.cpx_del_mfda[ox], out.cpx_del_ldt[ox])) {
+                out.cpx_del_mfda[ox] = INT64_MIN;
+                out.cpx_del_ldt[ox] = LDT_NONE_U32;
             }
-            uint64_t s0 = out.cpx_start[o];
-            uint32_t nc2 = out.cpx_count[o], w = 0;
+            uint64_t s0 = out.cpx_start[ox];
+            uint32_t nc2 = out.cpx_count[ox], w = 0;
             for (uint32_t e = 0; e < nc2; e++) {
                 if (out.cpx.ts[s0 + e] <= am) continue;
                 gc_cpx_move(out, s0 + w, s0 + e);
                 w++;
             }
-            out.cpx_count[o] = w;
-            bool cpx_alive = w || !(out.cpx_del_mfda[o] == INT64_MIN &&
-                                    out.cpx_del_ldt[o] == LDT_NONE_U32);
-            if (!cpx_alive) f &= ~PF_HAS_CPX;
-            else any_cell = true;
+            out.cpx_count[ox] = w;
+            bool cpx_alive = w || !(out.cpx_del_mfda[ox] == INT64_MIN &&
+                                    out.cpx_del_ldt[ox] == LDT_NONE_U32);
+            out.cpx_present[ox] = cpx_alive;
+            any_cpx |= cpx_alive;
         }
+        if (any_cpx) any_cell = true;
+        else f &= ~PF_HAS_CPX;
     } else {
         for (uint32_t c = 0; c < sch.n_cols; c++)
             if (out.cell_flags[o * sch.n_cols + c] & CELLF_PRESENT) any_cell = true;
@@ -2899,29 +2974,33 @@ __device__ inline bool gc_filter_row_vs(UnfCols& out, uint64_t o, const UnfCols&
         }
         any_cell = true;
     }
-    if (sch.n_cpx && (f & PF_HAS_CPX)) {
-        // complex branch of Rows.removeShadowedCells (Rows.java:298-316):
+    bool any_cpx = false;
+    for (uint32_t x = 0; x < sch.n_cpx && (f & PF_HAS_CPX); x++) {
+        // complex branch of Rows.removeShadowedCells (Rows.java:298-316),
+        // against the source row's column of the same index:
         // data complexDeletion survives iff it supersedes
         // max(updateDt, deletion) and then raises the bar; then per-path
         // Cells.addNonShadowedComplex against the source's cells
-        bool b_has = tin.flags[t] & PF_HAS_CPX;
-        int64_t udm = b_has ? tin.cpx_del_mfda[t] : INT64_MIN;
-        uint32_t udl = b_has ? tin.cpx_del_ldt[t] : LDT_NONE_U32;
+        const uint64_t ox = o * sch.n_cpx + x, tx = t * sch.n_cpx + x;
+        if (!out.cpx_present[ox]) continue;
+        bool b_has = (tin.flags[t] & PF_HAS_CPX) && tin.cpx_present[tx];
+        int64_t udm = b_has ? tin.cpx_del_mfda[tx] : INT64_MIN;
+        uint32_t udl = b_has ? tin.cpx_del_ldt[tx] : LDT_NONE_U32;
         int64_t mm = dm;
         uint32_t ml = dl;
         if (dtp_sup(udm, udl, mm, ml)) { mm = udm; ml = udl; }
-        bool keep_del = dtp_sup(out.cpx_del_mfda[o], out.cpx_del_ldt[o], mm, ml);
+        bool keep_del = dtp_sup(out.cpx_del_mfda[ox], out.cpx_del_ldt[ox], mm, ml);
         if (keep_del) {
-            mm = out.cpx_del_mfda[o];
-            ml = out.cpx_del_ldt[o];
+            mm = out.cpx_del_mfda[ox];
+            ml = out.cpx_del_ldt[ox];
         } else {
-            out.cpx_del_mfda[o] = INT64_MIN;
-            out.cpx_del_ldt[o] = LDT_NONE_U32;
+            out.cpx_del_mfda[ox] = INT64_MIN;
+            out.cpx_del_ldt[ox] = LDT_NONE_U32;
         }
-        uint64_t s0 = out.cpx_start[o];
-        uint32_t nc2 = out.cpx_count[o], w = 0;
-        uint64_t tb0 = b_has ? tin.cpx_start[t] : 0;
-        uint32_t tn = b_has ? tin.cpx_count[t] : 0, bi = 0;
+        uint64_t s0 = out.cpx_start[ox];
+        uint32_t nc2 = out.cpx_count[ox], w = 0;
+        uint64_t tb0 = b_has ? tin.cpx_start[tx] : 0;
+        uint32_t tn = b_has ? tin.cpx_count[tx] : 0, bi = 0;
         for (uint32_t e = 0; e < nc2; e++) {
             uint64_t xe = s0 + e;
             bool have_b = false;
@@ -2944,10 +3023,12 @@ __device__ inline bool gc_filter_row_vs(UnfCols& out, uint64_t o, const UnfCols&
             gc_cpx_move(out, s0 + w, xe);
             w++;
         }
-        out.cpx_count[o] = w;
-        if (!w && !keep_del) f &= ~PF_HAS_CPX;
-        else any_cell = true;
+        out.cpx_count[ox] = w;
+        out.cpx_present[ox] = w || keep_del;
+        any_cpx |= w || keep_del;
     }
+    if (any_cpx) any_cell = true;
+    else f &= ~PF_HAS_CPX;
     bool keep = (f & (PF_LIVE_TS | PF_ROW_DEL)) || any_cell;
     out.flags[o] = keep ? (f | PF_HAS_ROW) : 0;
     return keep;
@@ -2979,13 +3060,15 @@ __device__ inline void gc_copy_unf(UnfCols& dst, uint64_t d, const UnfCols& src,
         dst.val_addr[dc] = src.val_addr[sc];
         dst.val_len[dc] = src.val_len[sc];
     }
-    if (sch.n_cpx) {
+    for (uint32_t x = 0; x < sch.n_cpx; x++) {
         // the cpx CELL arena is shared (aliased) between src and dst in the
-        // gc path; only the per-row segment descriptors are copied
-        dst.cpx_del_mfda[d] = src.cpx_del_mfda[s];
-        dst.cpx_del_ldt[d] = src.cpx_del_ldt[s];
-        dst.cpx_start[d] = src.cpx_start[s];
-        dst.cpx_count[d] = src.cpx_count[s];
+        // gc path; only the per-column segment descriptors are copied
+        uint64_t dx = d * sch.n_cpx + x, sx = s * sch.n_cpx + x;
+        dst.cpx_present[dx] = src.cpx_present[sx];
+        dst.cpx_del_mfda[dx] = src.cpx_del_mfda[sx];
+        dst.cpx_del_ldt[dx] = src.cpx_del_ldt[sx];
+        dst.cpx_start[dx] = src.cpx_start[sx];
+        dst.cpx_count[dx] = src.cpx_count[sx];
     }
 }
 
@@ -3172,6 +3255,54 @@ __global__ void k_garbage_filter(OutParts dp, uint64_t nd, OutParts tp, UnfCols 
     dp.row_count[g] = oc;
 }
 
+// ComplexColumnData.purge over every present complex column of output row
+// `o` (deferred-purge variant over the shared cpx arena); returns whether any
+// column is left.
+__device__ inline bool purge_row_cpx(UnfCols& out, uint64_t o, uint32_t n_cpx,
+                                     const PurgeParams2& pp, int64_t token) {
+    bool any_cpx = false;
+    for (uint32_t x = 0; x < n_cpx; x++) {
+        // ComplexColumnData.purge (ComplexColumnData.java:212-216),
+        // deferred-purge variant over the shared cpx arena
+        const uint64_t ox = o * n_cpx + x;
+        if (!out.cpx_present[ox]) continue;
+        if (out.cpx_del_mfda[ox] != INT64_MIN &&
+            should_purge2(pp, token, out.cpx_del_mfda[ox], ldt_long(out.cpx_del_ldt[ox]))) {
+            out.cpx_del_mfda[ox] = INT64_MIN;
+            out.cpx_del_ldt[ox] = LDT_NONE_U32;
+        }
+        uint64_t s0 = out.cpx_start[ox];
+        uint32_t nc2 = out.cpx_count[ox], wx = 0;
+        for (uint32_t e = 0; e < nc2; e++) {
+            uint64_t xe = s0 + e;
+            int64_t cts = out.cpx.ts[xe];
+            uint32_t cldt = out.cpx.ldt[xe];
+            int32_t cttl = out.cpx.ttl[xe];
+            bool live_cell =
+                cldt == LDT_NONE_U32 || (cttl != 0 && pp.now_sec < ldt_long(cldt));
+            if (!live_cell) {
+                if (should_purge2(pp, token, cts, ldt_long(cldt))) continue;
+                if (cttl != 0) {
+                    int64_t nldt = ldt_long(cldt) - cttl;
+                    if (should_purge2(pp, token, cts, nldt)) continue;
+                    out.cpx.ldt[xe] = ldt_u32(nldt);
+                    out.cpx.ttl[xe] = 0;
+                    out.cpx.flags[xe] = CELLF_PRESENT;  // expired -> tombstone
+                    out.cpx.val_len[xe] = 0;
+                }
+            }
+            gc_cpx_move(out, s0 + wx, xe);
+            wx++;
+        }
+        out.cpx_count[ox] = wx;
+        bool xp = wx || out.cpx_del_mfda[ox] != INT64_MIN ||
+                  out.cpx_del_ldt[ox] != LDT_NONE_U32;
+        out.cpx_present[ox] = xp;
+        any_cpx |= xp;
+    }
+    return any_cpx;
+}
+
 // PurgeFunction pass over an OutParts arena (the garbage-collect path defers
 // purge until after the filter; mirrors oracle purge_partition). Compacts
 // kept unfiltereds in place and refreshes keep/first/last bookkeeping.
@@ -3310,44 +3441,9 @@ __global__ void k_purge_parts(OutParts op, UnfCols out, uint64_t n, SchemaParams
                 }
                 any_cell = true;
             }
-            if (sch.n_cpx && (f & PF_HAS_CPX)) {
-                // ComplexColumnData.purge (ComplexColumnData.java:212-216),
-                // deferred-purge variant over the shared cpx arena
-                if (out.cpx_del_mfda[o] != INT64_MIN &&
-                    should_purge2(pp, token, out.cpx_del_mfda[o], ldt_long(out.cpx_del_ldt[o]))) {
-                    out.cpx_del_mfda[o] = INT64_MIN;
-                    out.cpx_del_ldt[o] = LDT_NONE_U32;
-                }
-                uint64_t s0 = out.cpx_start[o];
-                uint32_t nc2 = out.cpx_count[o], wx = 0;
-                for (uint32_t e = 0; e < nc2; e++) {
-                    uint64_t xe = s0 + e;
-                    int64_t cts = out.cpx.ts[xe];
-                    uint32_t cldt = out.cpx.ldt[xe];
-                    int32_t cttl = out.cpx.ttl[xe];
-                    bool live_cell =
-                        cldt == LDT_NONE_U32 || (cttl != 0 && pp.now_sec < ldt_long(cldt));
-                    if (!live_cell) {
-                        if (should_purge2(pp, token, cts, ldt_long(cldt))) continue;
-                        if (cttl != 0) {
-                            int64_t nldt = ldt_long(cldt) - cttl;
-                            if (should_purge2(pp, token, cts, nldt)) continue;
-                            out.cpx.ldt[xe] = ldt_u32(nldt);
-                            out.cpx.ttl[xe] = 0;
-                            out.cpx.flags[xe] = CELLF_PRESENT;  // expired -> tombstone
-                            out.cpx.val_len[xe] = 0;
-                        }
-                    }
-                    gc_cpx_move(out, s0 + wx, xe);
-                    wx++;
-                }
-                out.cpx_count[o] = wx;
-                if (!wx && out.cpx_del_mfda[o] == INT64_MIN &&
-                    out.cpx_del_ldt[o] == LDT_NONE_U32)
-                    f &= ~PF_HAS_CPX;
-                else
-                    any_cell = true;
-            }
+            bool any_cpx = (f & PF_HAS_CPX) && purge_row_cpx(out, o, sch.n_cpx, pp, token);
+            if (any_cpx) any_cell = true;
+            else f &= ~PF_HAS_CPX;
             if (!(f & (PF_LIVE_TS | PF_ROW_DEL)) && !any_cell) f = 0;
             else if (pp.enforce_strict_liveness && !(f & PF_LIVE_TS) && !(f & PF_ROW_DEL)) f = 0;
             out.flags[o] = f ? (f | PF_HAS_ROW) : 0;
@@ -3677,6 +3773,7 @@ __global__ void k_gen_fill2(GenParams2 gp, const MRec* sorted, const uint64_t* i
         out.rkind[o] = kind;
         put_ck(o, ck, true, false, NCK == 2 ? 1 : NCK);  // 2-col mode: prefix bounds
         if (gp.complex_pct) {
+            out.cpx_present[o] = 0;
             out.cpx_del_mfda[o] = INT64_MIN;
             out.cpx_del_ldt[o] = LDT_NONE_U32;
             out.cpx_start[o] = cpx_cur;
@@ -3706,6 +3803,7 @@ __global__ void k_gen_fill2(GenParams2 gp, const MRec* sorted, const uint64_t* i
         out.live_ttl[o] = 0;
         out.live_let[o] = NO_DELETION_TIME;
         if (gp.complex_pct) {
+            out.cpx_present[o] = 0;
             out.cpx_del_mfda[o] = INT64_MIN;
             out.cpx_del_ldt[o] = LDT_NONE_U32;
             out.cpx_start[o] = cpx_cur;
@@ -3800,6 +3898,7 @@ __global__ void k_gen_fill2(GenParams2 gp, const MRec* sorted, const uint64_t* i
             // complex column 'zm': dedup+sorted map cells (oracle put_complex)
             if (gp.complex_pct && gen2_has_cpx(gp, id, rowj)) {
                 out.flags[o] |= PF_HAS_CPX;
+                out.cpx_present[o] = 1;
                 if (gen2_has_cpx_del(gp, id, rowj)) {
                     out.cpx_del_mfda[o] = ts - 1;
                     out.cpx_del_ldt[o] = gen2_ldt(gp, id * 5 + rowj, 0xCD);

@@ -276,15 +276,25 @@ struct HostSchema {
     std::vector<int32_t> col_fixed;     // SIMPLE regular columns only
     std::vector<int32_t> ck_widths;     // per clustering column
     std::vector<int32_t> static_fixed;  // per static column
-    uint32_t n_cpx = 0;                 // one complex (map<blob,blob>) column, last
+    uint32_t n_cpx = 0;                 // trailing complex (map<blob,blob>) columns
     bool counters = false;              // counter table (every column CounterColumnType)
 };
 // The one resolver: rejects every layout the engine cannot walk.
 inline HostSchema resolve_schema(const HStatistics& st) {
     HostSchema hs;
     const auto& rcols = st.regular_cols;
+    const std::string map_bb =
+        "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,"
+        "org.apache.cassandra.db.marshal.BytesType)";
     for (size_t ci = 0; ci < rcols.size(); ci++) {
         const std::string& ct = rcols[ci].second;
+        // the complex columns are the trailing run of the header's regular
+        // columns (engine layout constraint: subset-bitmap bit n_simple + x
+        // is complex column x; the generator names its one 'zm' so name
+        // order puts it last)
+        if (hs.n_cpx && ct != map_bb)
+            throw std::runtime_error(
+                "complex columns must follow every simple regular column");
         if (ct == "org.apache.cassandra.db.marshal.LongType") hs.col_fixed.push_back(8);
         else if (ct == "org.apache.cassandra.db.marshal.Int32Type") hs.col_fixed.push_back(4);
         else if (ct == "org.apache.cassandra.db.marshal.BytesType" ||
@@ -295,17 +305,15 @@ inline HostSchema resolve_schema(const HStatistics& st) {
             hs.col_fixed.push_back(-1);
             hs.counters = true;
         }
-        else if (ct == "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,org.apache.cassandra.db.marshal.BytesType)") {
-            // one complex column, and it must be the LAST regular column
-            // (engine layout constraint; the generator names it 'zm' so
-            // name order puts it last)
-            if (hs.n_cpx || ci + 1 != rcols.size())
-                throw std::runtime_error("at most one complex column, as the last regular column");
-            hs.n_cpx = 1;
+        else if (ct == map_bb) {
+            hs.n_cpx++;
         } else {
             throw std::runtime_error("unsupported column type " + ct);
         }
     }
+    // the column-subset bitmap (Columns.serializeSubset) stays below 64 bits
+    if (hs.col_fixed.size() + hs.n_cpx > 63)
+        throw std::runtime_error("at most 63 regular columns (simple + complex) supported");
     if (hs.counters) {
         // counter tables hold only counter columns (CreateTableStatement
         // forbids mixing); complex/static columns are rejected with them

@@ -268,6 +268,14 @@ typedef struct gpuc_cpx_cell {  /* one complex (collection) cell */
     uint32_t path_len;
 } gpuc_cpx_cell;
 
+typedef struct gpuc_cpx_col {   /* one complex column of one row */
+    uint8_t present;            /* column set on this row */
+    int64_t del_mfda;           /* complexDeletion (INT64_MIN = live) */
+    uint32_t del_ldt;           /* GPUC_LDT_NONE = live */
+    uint32_t n_cells;
+    const gpuc_cpx_cell* cells; /* CellPath order */
+} gpuc_cpx_col;
+
 typedef struct gpuc_unfiltered {
     uint8_t kind;               /* ClusteringPrefix.Kind ordinal
                                  * (ClusteringPrefix.java:65-85): 4 = row,
@@ -285,12 +293,19 @@ typedef struct gpuc_unfiltered {
     int64_t open_mfda;          /* boundary markers: open deletion */
     uint32_t open_ldt;
     const gpuc_cell* cells;     /* rows: schema->n_cols entries (the complex
-                                 * column's entry is ignored; see cpx_*) */
+                                 * columns' entries are ignored; see cpx_*) */
+    /* legacy single-column form, read only while cpx_cols == NULL: */
     uint8_t has_cpx;            /* complex column present on this row */
     int64_t cpx_del_mfda;       /* complexDeletion */
     uint32_t cpx_del_ldt;
     uint32_t n_cpx_cells;
     const gpuc_cpx_cell* cpx_cells;  /* in CellPath order */
+    /* non-NULL: schema->n_cpx entries in header order, and the five legacy
+     * fields above are ignored. NULL: the legacy fields describe the one
+     * complex column; with schema->n_cpx >= 2 a row with has_cpx set and
+     * NULL cpx_cols is an error. Each column's paths must be strictly
+     * increasing in CellPath order (unsigned bytes, shorter first). */
+    const gpuc_cpx_col* cpx_cols;
 } gpuc_unfiltered;
 
 typedef struct gpuc_flush_part {
@@ -318,8 +333,8 @@ typedef struct gpuc_flush_schema {
     const char* key_type;
     uint32_t n_ck;
     const char* const* ck_types;
-    uint32_t n_cols;            /* regular columns, header order; a complex
-                                 * (MapType) column must be LAST */
+    uint32_t n_cols;            /* regular columns, header order; the complex
+                                 * (MapType) columns must be the LAST n_cpx */
     const uint8_t* const* col_names;
     const uint32_t* col_name_lens;
     const char* const* col_types;
@@ -327,7 +342,8 @@ typedef struct gpuc_flush_schema {
     const uint8_t* const* static_names;
     const uint32_t* static_name_lens;
     const char* const* static_types;
-    uint32_t n_cpx;             /* 0/1: last regular column is complex */
+    uint32_t n_cpx;             /* number of trailing complex columns
+                                 * (map<blob,blob>; n_cols <= 63) */
     uint32_t column_index_size; /* 0 = 64 KiB */
     uint32_t snappy;            /* chunk codec for the output */
     uint32_t bti;               /* write the `da` (trie-indexed) components */
@@ -357,8 +373,9 @@ int gpuc_scrub(const char* input_base, const char* output_base, int32_t device,
 /* Verify one sstable (Verifier.java / sstableverify --extended semantics):
  * CompressionInfo frame walk, per-chunk CRC32, full row-format walk,
  * strict DecoratedKey order, Digest.crc32 recomputation, bloom-filter
- * rebuild compared against Filter.db. GPUC_OK or GPUC_ERR_FORMAT with a
- * message. */
+ * rebuild compared against Filter.db. A `da` (trie-indexed) sstable takes
+ * its partition positions from Partitions.db / Rows.db instead of Index.db.
+ * GPUC_OK or GPUC_ERR_FORMAT with a message. */
 int gpuc_verify(const char* input_base, int32_t device, char* error, size_t error_len);
 
 /* Diagnostic: chunk-compress a host buffer exactly as the writer does (the
