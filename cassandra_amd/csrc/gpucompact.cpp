@@ -1,6 +1,7 @@
-// PRODUCT — host side of libcassandra_gpucompact: file I/O, sstable metadata
-// (CompressionInfo/Statistics/Summary/TOC/Digest) assembly, and the HIP
-// pipeline orchestration. Compiled as one TU with kernels.hip by hipcc.
+// PRODUCT — host side of libcassandra_gpucompact: input file I/O and the HIP
+// pipeline orchestration. The bytes of the small output components are
+// decided in sstable_out.h (host-only, CPU-tested); the input metadata is
+// parsed in sstable_meta.h. Compiled as one TU with kernels.hip by hipcc.
 //
 // The host does NO data-path compute: decompress/decode/merge/reconcile/
 // purge/serialize/compress/CRC/bloom all run in the kernels. There is no CPU
@@ -9,6 +10,7 @@
 #include "kernels_rows.hip"
 #include "bti_core.h"
 #include "sstable_meta.h"
+#include "sstable_out.h"
 #include "../../include/gpucompact.h"
 
 #include <algorithm>
@@ -37,18 +39,6 @@ namespace gpuc {
             throw std::runtime_error(std::string("HIP error: ") +                 \
                                      hipGetErrorString(_e) + " at " #x);          \
     } while (0)
-
-// ---------------------------------------------------------------------------
-// host byte helpers
-// ---------------------------------------------------------------------------
-static void put_be16(bytes& o, uint16_t v) { o.push_back(v >> 8); o.push_back((uint8_t)v); }
-static void put_be32(bytes& o, uint32_t v) { for (int i = 3; i >= 0; i--) o.push_back((uint8_t)(v >> (8 * i))); }
-static void put_be64(bytes& o, uint64_t v) { for (int i = 7; i >= 0; i--) o.push_back((uint8_t)(v >> (8 * i))); }
-static void put_uvint(bytes& o, uint64_t v) {
-    uint8_t tmp[9];
-    int n = uvint_put(tmp, v);
-    o.insert(o.end(), tmp, tmp + n);
-}
 
 // grow-only pinned staging buffers, reused across calls (hipHostMalloc is
 // expensive; a compaction service reuses its staging arenas the same way)
@@ -117,34 +107,6 @@ static void read_file_range(const std::string& path, uint8_t* dst, uint64_t off,
     for (auto& x : th) x.join();
 }
 
-static void write_file_parallel(const std::string& path, const uint8_t* p, size_t n, int nthreads = 4) {
-    // create + size, then threaded pwrite
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!f) throw std::runtime_error("cannot create " + path);
-    fclose(f);
-    if (n == 0) return;
-    if (truncate(path.c_str(), (off_t)n) != 0) throw std::runtime_error("truncate " + path);
-    std::vector<std::thread> th;
-    size_t per = (n + nthreads - 1) / nthreads;
-    for (int t = 0; t < nthreads; t++) {
-        size_t off = (size_t)t * per;
-        if (off >= n) break;
-        size_t len = std::min(per, n - off);
-        th.emplace_back([&, off, len]() {
-            int fd = open(path.c_str(), O_WRONLY);
-            if (fd < 0) return;
-            size_t done = 0;
-            while (done < len) {
-                ssize_t w = pwrite(fd, p + off + done, len - done, (off_t)(off + done));
-                if (w <= 0) break;
-                done += (size_t)w;
-            }
-            close(fd);
-        });
-    }
-    for (auto& x : th) x.join();
-}
-
 static bytes read_file(const std::string& path) {
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) throw std::runtime_error("cannot open " + path);
@@ -156,211 +118,6 @@ static bytes read_file(const std::string& path) {
     fclose(f);
     return b;
 }
-static void write_file(const std::string& path, const uint8_t* p, size_t n) {
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!f) throw std::runtime_error("cannot create " + path);
-    if (n && fwrite(p, 1, n, f) != n) { fclose(f); throw std::runtime_error("short write " + path); }
-    fclose(f);
-}
-
-// ---------------------------------------------------------------------------
-// output component assembly (host; small metadata only — spec'd identically in
-// oracle/src/sstable.cpp so GPU and oracle outputs are byte-identical)
-// ---------------------------------------------------------------------------
-static void put_type_str(bytes& o, const std::string& s) {
-    put_uvint(o, s.size());
-    o.insert(o.end(), s.begin(), s.end());
-}
-static std::vector<int64_t> est_hist_offsets(int size) {
-    std::vector<int64_t> off;
-    int64_t last = 1;
-    off.push_back(1);
-    for (int i = 1; i < size; i++) {
-        int64_t next = (int64_t)llround((double)last * 1.2);
-        if (next == last) next++;
-        off.push_back(next);
-        last = next;
-    }
-    return off;
-}
-static void put_est_hist(bytes& o, const std::vector<int64_t>& off, const uint64_t* buckets) {
-    put_be32(o, (uint32_t)(off.size() + 1));
-    for (size_t i = 0; i < off.size() + 1; i++) {
-        put_be64(o, (uint64_t)off[i == 0 ? 0 : i - 1]);
-        put_be64(o, buckets[i]);
-    }
-}
-// HyperLogLogPlus(13, 25) of the partition-key hash2_64 values (clearspring
-// stream-lib; MetadataCollector.java:180-183). SPARSE while under the
-// 0.75*m threshold with no flagged (low-bits-zero) key: (h >>> 39) << 1,
-// delta varints over the sorted set — this encoding byte-reproduces the
-// reference's own oa fixtures (oracle test_compaction_hll_fixture_pin).
-// NORMAL otherwise: 2^13 five-bit registers, six per big-endian 32-bit word.
-static bytes hll_bytes(const std::vector<uint64_t>& key_hashes) {
-    constexpr int P = 13, SP = 25;
-    bytes h;
-    put_be32(h, (uint32_t)-2);
-    auto pv = [&](uint32_t v) { while (v >= 0x80) { h.push_back((uint8_t)(v | 0x80)); v >>= 7; } h.push_back((uint8_t)v); };
-    pv(P); pv(SP);
-    std::set<uint32_t> sparse;
-    bool flagged = false;
-    const uint32_t threshold = (uint32_t)((1u << P) * 3 / 4);
-    for (uint64_t kh : key_hashes) {
-        uint32_t sidx = (uint32_t)(kh >> (64 - SP));
-        if ((sidx & ((1u << (SP - P)) - 1)) == 0) { flagged = true; break; }
-        sparse.insert(sidx << 1);
-        if (sparse.size() > threshold) break;
-    }
-    if (!flagged && sparse.size() <= threshold && key_hashes.size() <= threshold) {
-        pv(1 /*SPARSE*/);
-        pv((uint32_t)sparse.size());
-        uint32_t prev = 0;
-        for (uint32_t v : sparse) { pv(v - prev); prev = v; }
-    } else {
-        pv(0 /*NORMAL*/);
-        std::vector<uint8_t> regs(1u << P, 0);
-        for (uint64_t kh : key_hashes) {
-            uint32_t idx = (uint32_t)(kh >> (64 - P));
-            uint64_t w = (kh << P) | (1ull << (P - 1));
-            uint8_t rho = (uint8_t)(__builtin_clzll(w) + 1);
-            if (rho > regs[idx]) regs[idx] = rho;
-        }
-        uint32_t bits = (1u << P) / 6;
-        uint32_t reg_ints = (bits % 32 == 0) ? bits : bits + 1;  // RegisterSet.getSizeForCount
-        std::vector<uint32_t> M(reg_ints, 0);
-        for (uint32_t i = 0; i < (1u << P); i++)
-            M[i / 6] |= (uint32_t)regs[i] << (5 * (i % 6));
-        pv(reg_ints * 4);
-        for (uint32_t wv : M) put_be32(h, wv);
-    }
-    bytes o;
-    put_be32(o, (uint32_t)h.size());
-    o.insert(o.end(), h.begin(), h.end());
-    return o;
-}
-
-struct OutMeta {
-    // header (deltas) of the output sstable
-    HeaderStats hs;
-    std::string key_type;
-    std::vector<std::string> ck_types;  // empty = no clustering columns
-    std::vector<std::pair<bytes, std::string>> static_cols;
-    std::vector<std::pair<bytes, std::string>> regular_cols;
-    // collected stats
-    int64_t min_timestamp, max_timestamp, min_ldt, max_ldt;
-    int32_t min_ttl, max_ttl;
-    uint64_t total_rows, total_cells;
-    bool has_partition_deletions;
-    bytes first_key, last_key;
-    std::map<uint32_t, uint32_t> tomb_hist;
-    double compression_ratio;
-    uint64_t part_size_hist[156];
-    uint64_t cells_hist[119];
-    std::vector<uint64_t> key_hashes;  // hash2_64 per kept partition (HLL)
-};
-
-static bytes serialize_statistics_out(const OutMeta& m) {
-    bytes validation;
-    {
-        std::string pn = "org.apache.cassandra.dht.Murmur3Partitioner";
-        put_be16(validation, (uint16_t)pn.size());
-        validation.insert(validation.end(), pn.begin(), pn.end());
-        uint64_t fp;
-        double fpv = 0.01;
-        memcpy(&fp, &fpv, 8);
-        put_be64(validation, fp);
-    }
-    bytes compaction = hll_bytes(m.key_hashes);
-    bytes stats;
-    {
-        static const std::vector<int64_t> ps_off = est_hist_offsets(155);
-        static const std::vector<int64_t> ch_off = est_hist_offsets(118);
-        put_est_hist(stats, ps_off, m.part_size_hist);
-        put_est_hist(stats, ch_off, m.cells_hist);
-        put_be64(stats, (uint64_t)-1LL); put_be32(stats, 0);  // commitLogUpperBound NONE
-        put_be64(stats, (uint64_t)m.min_timestamp);
-        put_be64(stats, (uint64_t)m.max_timestamp);
-        put_be32(stats, ldt_u32(m.min_ldt));
-        put_be32(stats, ldt_u32(m.max_ldt));
-        put_be32(stats, (uint32_t)m.min_ttl);
-        put_be32(stats, (uint32_t)m.max_ttl);
-        uint64_t cr; double crv = m.compression_ratio; memcpy(&cr, &crv, 8); put_be64(stats, cr);
-        put_be32(stats, 100);  // TombstoneHistogram maxBinSize
-        put_be32(stats, (uint32_t)m.tomb_hist.size());
-        for (auto& [pt, cnt] : m.tomb_hist) { put_be64(stats, pt); put_be32(stats, cnt); }
-        put_be32(stats, 0);               // sstableLevel
-        put_be64(stats, 0);               // repairedAt
-        // improvedMinMax: clustering type list + covered Slice (spec'd with the
-        // oracle: BOTTOM..TOP bounds, no values)
-        put_uvint(stats, m.ck_types.size());
-        for (auto& t : m.ck_types) put_type_str(stats, t);
-        stats.push_back(1); put_be16(stats, 0);  // Slice start: INCL_START, 0 values
-        stats.push_back(6); put_be16(stats, 0);  // Slice end: INCL_END, 0 values
-        stats.push_back(0);               // hasLegacyCounterShards
-        put_be64(stats, m.total_cells);
-        put_be64(stats, m.total_rows);
-        put_be64(stats, (uint64_t)-1LL); put_be32(stats, 0);  // commitLogLowerBound NONE
-        put_be32(stats, 0);               // commitLogIntervals empty
-        stats.push_back(0);               // pendingRepair null
-        stats.push_back(0);               // isTransient
-        stats.push_back(0);               // originatingHostId null
-        stats.push_back(m.has_partition_deletions ? 1 : 0);
-        put_uvint(stats, m.first_key.size());
-        stats.insert(stats.end(), m.first_key.begin(), m.first_key.end());
-        put_uvint(stats, m.last_key.size());
-        stats.insert(stats.end(), m.last_key.begin(), m.last_key.end());
-        uint64_t ts; double tsc = 0.0; memcpy(&ts, &tsc, 8); put_be64(stats, ts);
-    }
-    bytes header;
-    {
-        put_uvint(header, (uint64_t)(m.hs.min_ts - TIMESTAMP_EPOCH));
-        put_uvint(header, sext32(m.hs.min_ldt - DELETION_TIME_EPOCH));
-        put_uvint(header, sext32(m.hs.min_ttl));
-        put_type_str(header, m.key_type);
-        put_uvint(header, m.ck_types.size());
-        for (auto& t : m.ck_types) put_type_str(header, t);
-        put_uvint(header, m.static_cols.size());
-        for (auto& [name, t] : m.static_cols) {
-            put_uvint(header, name.size());
-            header.insert(header.end(), name.begin(), name.end());
-            put_type_str(header, t);
-        }
-        put_uvint(header, m.regular_cols.size());
-        for (auto& [name, t] : m.regular_cols) {
-            put_uvint(header, name.size());
-            header.insert(header.end(), name.begin(), name.end());
-            put_type_str(header, t);
-        }
-    }
-    const bytes* comps[4] = {&validation, &compaction, &stats, &header};
-    bytes out;
-    uint32_t crc = 0;
-    auto crc_int = [](uint32_t c, uint32_t v) {
-        uint8_t b[4] = {(uint8_t)(v >> 24), (uint8_t)(v >> 16), (uint8_t)(v >> 8), (uint8_t)v};
-        return crc32_update_bitwise(c, b, 4);
-    };
-    put_be32(out, 4);
-    crc = crc_int(0, 4);
-    put_be32(out, crc);
-    uint32_t pos = 4 + 8 * 4 + 2 * 4;
-    for (int i = 0; i < 4; i++) {
-        put_be32(out, i);
-        crc = crc_int(crc, i);
-        put_be32(out, pos);
-        crc = crc_int(crc, pos);
-        pos += comps[i]->size() + 4;
-    }
-    put_be32(out, crc);
-    for (int i = 0; i < 4; i++) {
-        out.insert(out.end(), comps[i]->begin(), comps[i]->end());
-        put_be32(out, crc32_update_bitwise(0, comps[i]->data(), comps[i]->size()));
-    }
-    return out;
-}
-
-// bloom spec for fp=0.01 (BloomCalculations; identical table in the oracle)
-struct HBloomSpec { int k; int buckets; };
-static HBloomSpec bloom_spec_001() { return {5, 10}; }  // computeBloomSpec(20, 0.01)
 
 // ---------------------------------------------------------------------------
 // device helpers (scan, merge)
@@ -669,186 +426,6 @@ struct WriteDeviceOut {
     double ms_sizes = 0, ms_serialize = 0, ms_compress = 0, ms_d2h = 0, ms_io = 0;
 };
 
-// shared device->files writer: sizes/scan -> serialize -> compress -> gather ->
-// D2H -> write all components. `st` is the device OutStats already filled by
-// reconcile (or gen); meta_* give header/schema info.
-// BTI (`da`) index post-pass: Partitions.db + Rows.db built on the host
-// from the big-format Index.db IMAGE the writer kernels already produced
-// (the image carries keys, data positions and the promoted-index blocks —
-// firstName/lastName clusterings, offsets, end-open markers — and those
-// blocks ARE the bti row-index blocks: rowIndexBlockSize ==
-// column_index_size, BtiFormatPartitionWriter.java:52). Byte layout pinned
-// against the reference's legacy_da fixtures through the oracle
-// (write_sstable(bti)) and the GPU parity suite.
-static void build_bti_from_index_image(const uint8_t* idx, uint64_t idx_len, uint64_t data_total,
-                                       const std::vector<int32_t>& ck_w,
-                                       bti::bytes* partitions_out, bti::bytes* rows_out) {
-    using bti::bytes;
-    uint64_t p = 0;
-    bytes rows_file;
-    std::vector<bti::BtiKeyEntry> pes;
-    std::vector<bti::BtiRowIndexBlockSpec> pending_specs;
-    std::vector<size_t> pending_idx;
-    std::vector<uint64_t> part_positions;
-    auto uvint = [&]() -> uint64_t {
-        uint8_t first = idx[p++];
-        int extra = 0;
-        uint8_t x = first;
-        while (x & 0x80) { extra++; x <<= 1; }
-        uint64_t r = first & (uint8_t)(0xFFu >> extra);
-        for (int i = 0; i < extra; i++) r = (r << 8) | idx[p++];
-        return r;
-    };
-    auto svint = [&]() -> int64_t {
-        uint64_t u = uvint();
-        return (int64_t)(u >> 1) ^ -(int64_t)(u & 1);
-    };
-    struct Blk {
-        bytes first_bc, last_bc;
-        uint64_t offset = 0;
-        bool has_open = false;
-        int64_t open_m = 0;
-        uint32_t open_l = 0;
-    };
-    auto parse_prefix = [&]() -> bytes {
-        uint8_t kind = idx[p++];
-        uint32_t nv;
-        if (kind != 4) {
-            nv = ((uint32_t)idx[p] << 8) | idx[p + 1];
-            p += 2;
-        } else {
-            nv = (uint32_t)ck_w.size();
-        }
-        std::vector<std::pair<const uint8_t*, uint32_t>> comps;
-        std::vector<int32_t> widths;
-        if (nv) {
-            (void)uvint();  // 32-batch null header (0: all present)
-            for (uint32_t c = 0; c < nv; c++) {
-                uint32_t len = ck_w[c] > 0 ? (uint32_t)ck_w[c] : (uint32_t)uvint();
-                comps.push_back({idx + p, len});
-                widths.push_back(ck_w[c]);
-                p += len;
-            }
-        }
-        return bti::byte_comparable_clustering(comps, widths, kind);
-    };
-    while (p < idx_len) {
-        uint32_t klen = ((uint32_t)idx[p] << 8) | idx[p + 1];
-        p += 2;
-        const uint8_t* key = idx + p;
-        p += klen;
-        uint64_t pos = uvint();
-        uint64_t promoted = uvint();
-        int64_t idxpos = ~(int64_t)pos;
-        if (promoted > 0) {
-            uint64_t pend = p + promoted;
-            (void)uvint();  // headerLength
-            bool pdel_live = idx[p] == 0x80;
-            int64_t pdm = 0;
-            uint32_t pdl = 0;
-            if (pdel_live) {
-                p += 1;
-            } else {
-                uint64_t m2 = 0;
-                for (int i = 0; i < 8; i++) m2 = (m2 << 8) | idx[p + i];
-                pdm = (int64_t)m2;
-                pdl = ((uint32_t)idx[p + 8] << 24) | ((uint32_t)idx[p + 9] << 16) |
-                      ((uint32_t)idx[p + 10] << 8) | idx[p + 11];
-                p += 12;
-            }
-            uint64_t nblocks = uvint();
-            std::vector<Blk> blocks;
-            for (uint64_t b = 0; b < nblocks; b++) {
-                Blk bk;
-                bk.first_bc = parse_prefix();
-                bk.last_bc = parse_prefix();
-                bk.offset = uvint();
-                (void)svint();  // width - 64KiB (unused here)
-                bk.has_open = idx[p++] != 0;
-                if (bk.has_open) {
-                    if (idx[p] == 0x80) {
-                        bk.has_open = false;
-                        p += 1;
-                    } else {
-                        uint64_t m3v = 0;
-                        for (int i = 0; i < 8; i++) m3v = (m3v << 8) | idx[p + i];
-                        bk.open_m = (int64_t)m3v;
-                        bk.open_l = ((uint32_t)idx[p + 8] << 24) | ((uint32_t)idx[p + 9] << 16) |
-                                    ((uint32_t)idx[p + 10] << 8) | idx[p + 11];
-                        p += 12;
-                    }
-                }
-                blocks.push_back(std::move(bk));
-            }
-            p = pend;  // skip the block-offsets u32 table
-            bti::BtiRowIndexBlockSpec spec;
-            spec.partition_key.assign(key, key + klen);
-            spec.data_pos = pos;
-            spec.block_count = blocks.size();
-            spec.pdel_live = pdel_live;
-            spec.pdel_mfda = pdm;
-            spec.pdel_ldt = pdl;
-            bytes prev_sep, prev_max;
-            for (size_t b = 0; b < blocks.size(); b++) {
-                bytes bkey;
-                if (b > 0) bkey = bti::bti_separator_gt(blocks[b - 1].last_bc, blocks[b].first_bc);
-                bool has_od = b > 0 && blocks[b - 1].has_open;
-                int ob = 1;
-                while (blocks[b].offset >> (8 * ob - 1)) ob++;  // signed SizedInts
-                bti::BtiRowIndexBlockSpec::Entry e;
-                e.prefix = bkey;
-                e.pb = ob | (has_od ? 8 : 0);
-                for (int i = ob - 1; i >= 0; i--)
-                    e.payload.push_back((uint8_t)(blocks[b].offset >> (8 * i)));
-                if (has_od) {
-                    for (int i = 7; i >= 0; i--)
-                        e.payload.push_back((uint8_t)((uint64_t)blocks[b - 1].open_m >> (8 * i)));
-                    for (int i = 3; i >= 0; i--)
-                        e.payload.push_back((uint8_t)(blocks[b - 1].open_l >> (8 * i)));
-                }
-                spec.entries.push_back(std::move(e));
-                prev_sep = bkey;
-                prev_max = blocks[b].last_bc;
-            }
-            // final nudge entry; its payload (partition length - 1, the
-            // END_OF_PARTITION byte's offset) is patched once the next
-            // partition's position is known
-            size_t cm = 0;
-            while (cm < prev_max.size() && cm < prev_sep.size() && prev_max[cm] == prev_sep[cm]) cm++;
-            bti::BtiRowIndexBlockSpec::Entry fin;
-            fin.prefix = bti::bti_nudge(prev_max, cm);
-            spec.entries.push_back(std::move(fin));
-            pending_specs.push_back(std::move(spec));
-            pending_idx.push_back(pes.size());
-        }
-        bti::BtiKeyEntry e;
-        int64_t tok = murmur3_token(key, klen);
-        e.byte_comparable = bti::bti_byte_comparable_m3(tok, bytes(key, key + klen));
-        e.raw_key.assign(key, key + klen);
-        uint64_t h2[2];
-        murmur3_128(key, klen, 0, h2);
-        e.hash_bits = (uint8_t)h2[1];  // DecoratedKey.filterHashLowerBits
-        e.idxpos = idxpos;
-        pes.push_back(std::move(e));
-        part_positions.push_back(pos);
-    }
-    for (size_t i = 0; i < pending_specs.size(); i++) {
-        auto& spec = pending_specs[i];
-        size_t pi = pending_idx[i];
-        uint64_t next_pos = pi + 1 < part_positions.size() ? part_positions[pi + 1] : data_total;
-        uint64_t endoff = next_pos - spec.data_pos - 1;
-        auto& fin = spec.entries.back();
-        int ob = 1;
-        while (endoff >> (8 * ob - 1)) ob++;
-        fin.pb = ob;
-        fin.payload.clear();
-        for (int b = ob - 1; b >= 0; b--) fin.payload.push_back((uint8_t)(endoff >> (8 * b)));
-        pes[pi].idxpos = (int64_t)bti::append_bti_row_index(rows_file, spec);
-    }
-    *partitions_out = bti::write_bti_partitions(pes);
-    *rows_out = std::move(rows_file);
-}
-
 // The one place chunk-compress kernels are launched (sstable writer and
 // gpuc_compress_buffer): m chunks of chunk_len bytes (last one short) from
 // d_data -> payload slots of `stride` bytes + per-chunk size and CRC32.
@@ -954,7 +531,8 @@ struct DecodedFile {
 struct DevSchema {
     DevBuf ck_w, col_fixed, static_fixed;
     // hs is read by async copies: it must outlive the next synchronise of `stream`
-    SchemaParams upload(const HostSchema& hs, hipStream_t stream) {
+    SchemaParams upload(const HostSchema& hs, hipStream_t stream,
+                        uint32_t column_index_size = 64 * 1024) {
         auto up = [&](DevBuf& d, const std::vector<int32_t>& h) {
             d.alloc(h.size() * 4 + 8);
             if (!h.empty())
@@ -970,7 +548,7 @@ struct DevSchema {
         sch.counters = hs.counters ? 1u : 0u;
         sch.n_static = (uint32_t)hs.static_fixed.size();
         sch.static_fixed = up(static_fixed, hs.static_fixed);
-        sch.column_index_size = 64 * 1024;
+        sch.column_index_size = column_index_size;
         return sch;
     }
 };
@@ -1034,22 +612,193 @@ static void parse_input(ParsedInput& in, const DevBuf& d_srcs, uint32_t n_srcs, 
     rows_pass(sch.n_cpx ? in.cpxbase.as<uint64_t>() : nullptr);
 }
 
+// ---------------------------------------------------------------------------
+// group/reconcile back end shared by compact_one (data pass and
+// garbage-collect source pass) and gpuc_scrub: sorted records -> groups ->
+// per-group row sums -> output buffers -> k_reconcile_rows. Separate steps, so
+// a caller can poll for cancellation, trace and record events between them.
+// Every step issues on the stream it is given, and none launches an empty grid.
+// ---------------------------------------------------------------------------
+struct Groups {
+    const MRec* sorted = nullptr;  // n_recs records in DecoratedKey order
+    uint64_t n_recs = 0;
+    DevBuf head, start, count, rows;
+    uint64_t n = 0;           // groups (distinct partition keys)
+    uint64_t total_rows = 0;  // upper bound of the reconciled unfiltereds
+};
+// step 1: group starts and g.n; synchronises to read the count
+static void find_groups(Groups& g, const MRec* d_sorted, uint64_t n_recs, const KeyLut& lut,
+                        hipStream_t stream) {
+    g.sorted = d_sorted;
+    g.n_recs = n_recs;
+    g.head.alloc(n_recs * 8 + 8);
+    g.start.alloc(n_recs * 8 + 8);
+    g.count.alloc(8);
+    if (n_recs) {
+        const dim3 grid((uint32_t)((n_recs + 255) / 256)), block(256);
+        hipLaunchKernelGGL(k_group_heads, grid, block, 0, stream, d_sorted, n_recs,
+                           g.head.as<uint64_t>(), lut);
+        exscan_u64(g.head.as<uint64_t>(), n_recs, stream);
+        hipLaunchKernelGGL(k_group_starts2, grid, block, 0, stream, d_sorted, n_recs,
+                           g.head.as<uint64_t>(), g.start.as<uint64_t>(), g.count.as<uint64_t>(),
+                           lut);
+    } else {
+        HIP_CHECK(hipMemsetAsync(g.count.p, 0, 8, stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(&g.n, g.count.p, 8, hipMemcpyDeviceToHost));
+}
+// step 2: rows of each group summed over its sources, scanned into row bases
+// (g.rows) and g.total_rows; exscan_u64 synchronises
+static void scan_group_rows(Groups& g, const DevBuf& d_srcbases, const ParsedCols& pc,
+                            hipStream_t stream) {
+    g.rows.alloc(g.n * 8 + 8);
+    if (g.n)
+        hipLaunchKernelGGL(k_group_row_sums, dim3((uint32_t)((g.n + 255) / 256)), dim3(256), 0,
+                           stream, g.sorted, g.start.as<uint64_t>(), g.n, g.n_recs,
+                           d_srcbases.as<uint32_t>(), pc, g.rows.as<uint64_t>());
+    g.total_rows = exscan_u64(g.rows.as<uint64_t>(), g.n, stream);
+}
+// step 3: the reconciled output. alloc() sizes it from the groups and resets
+// the stats; launch_reconcile() fills it. Two calls, because compact_one sets
+// up its purge parameters and records its reconcile event between them.
+struct Reconciled {
+    OutPartsBuf parts;
+    UnfColsBuf rows;
+    DevBuf stats;  // OutStats
+    void alloc(const Groups& g, const SchemaParams& sch, uint64_t total_in_cpx,
+               hipStream_t stream) {
+        parts.alloc(g.n ? g.n : 1, sch.n_static);
+        rows.alloc(g.total_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
+        if (sch.n_cpx) rows.alloc_cpx_arena(total_in_cpx);
+        stats.alloc(sizeof(OutStats));
+        init_outstats(stats, stream);
+    }
+};
+// n_sources picks the kernel's per-group version capacity
+static void launch_reconcile(const Groups& g, int n_sources, const DevBuf& d_srcbases,
+                             const ParsedInput& in, Reconciled& out, const SchemaParams& sch,
+                             const PurgeParams2& pp, const DevBuf& d_error, hipStream_t stream) {
+    if (!g.n) return;
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((uint32_t)((g.n + 255) / 256)), dim3(256), 0, stream,
+                           g.sorted, g.start.as<uint64_t>(), g.n, g.n_recs,
+                           d_srcbases.as<uint32_t>(), in.pc, in.rows.uc, out.parts.op,
+                           out.rows.uc, g.rows.as<uint64_t>(), sch, pp, out.stats.as<OutStats>(),
+                           d_error.as<unsigned long long>());
+    };
+    if (n_sources <= 8) launch(k_reconcile_rows<8>);
+    else if (n_sources <= 16) launch(k_reconcile_rows<16>);
+    else launch(k_reconcile_rows<64>);
+}
+
+// merged-context arena of a counter table: capacity = total input counter
+// bytes (any k-way merge result is bounded by the sum of its inputs).
+// Synchronises to read the total.
+static uint64_t counter_arena_cap(const ParsedInput& in, uint32_t n_cols, hipStream_t stream) {
+    DevBuf d_sum;
+    d_sum.alloc(8);
+    HIP_CHECK(hipMemsetAsync(d_sum.p, 0, 8, stream));
+    uint64_t n_cells = in.total_rows * n_cols;
+    if (n_cells)
+        hipLaunchKernelGGL(k_sum_vallen, dim3((uint32_t)((n_cells + 255) / 256)), dim3(256), 0,
+                           stream, in.rows.uc, n_cells, d_sum.as<unsigned long long>());
+    unsigned long long total_ctr = 0;
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(&total_ctr, d_sum.p, 8, hipMemcpyDeviceToHost));
+    return total_ctr + 64;
+}
+
+// capacity of the tombstone local-deletion-time list k_collect_rows appends to
+static uint32_t tomb_list_cap(uint64_t rows, uint64_t cpx_cells, uint64_t parts,
+                              const SchemaParams& sch) {
+    return (uint32_t)std::min<uint64_t>(rows * ((uint64_t)sch.n_cols + sch.n_cpx + 2) + cpx_cells +
+                                            parts * ((uint64_t)sch.n_static + 2) + 1024,
+                                        400000000ull);
+}
+
+// OutStats keeps its signed minima and maxima sign-flipped (i64 ^ SIGN, as
+// u64); `none` is what a slot nothing was folded into decodes to
+static int64_t unflip(unsigned long long v) { return (int64_t)(v ^ 0x8000000000000000ULL); }
+static int64_t unflip(unsigned long long v, unsigned long long untouched, int64_t none) {
+    return v == untouched ? none : unflip(v);
+}
+
+// Header of freshly built rows (flush, generate): SerializationHeader.make
+// takes the EncodingStats of the rows, so k_collect_rows runs once ahead of
+// the writer, the minima are read back (synchronises), and the stats are
+// re-initialised for the writer's own collect. n_cols is the cell stride of
+// `rows`.
+static HeaderStats fresh_rows_header(const OutPartsBuf& opb, const UnfColsBuf& rows,
+                                     uint64_t n_parts, uint32_t n_cols, uint32_t n_cpx,
+                                     DevBuf& d_stats, DevBuf& d_tomb, uint32_t tomb_cap,
+                                     hipStream_t stream) {
+    d_stats.alloc(sizeof(OutStats));
+    init_outstats(d_stats, stream);
+    d_tomb.alloc((uint64_t)tomb_cap * 4);
+    hipLaunchKernelGGL(k_collect_rows, dim3((uint32_t)((n_parts + 255) / 256)), dim3(256), 0,
+                       stream, opb.op, rows.uc, n_parts, n_cols, n_cpx, d_stats.as<OutStats>(),
+                       d_tomb.as<uint32_t>(), tomb_cap);
+    OutStats hs0;
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(&hs0, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
+    HeaderStats hs;
+    hs.min_ts = unflip(hs0.min_ts_flip, ~0ull, TIMESTAMP_EPOCH);
+    hs.min_ldt = unflip(hs0.min_ldt_flip, ~0ull, DELETION_TIME_EPOCH);
+    if (hs.min_ldt == NO_DELETION_TIME) hs.min_ldt = DELETION_TIME_EPOCH;
+    hs.min_ttl = hs0.min_ttl == 0xFFFFFFFFu ? 0 : (int32_t)hs0.min_ttl;
+    init_outstats(d_stats, stream);
+    return hs;
+}
+
+// ---------------------------------------------------------------------------
+// shared device->files writer: sizes/scan -> serialize interleaved with
+// compress -> slab drain -> component tail. `d_stats` is the device OutStats
+// already filled by reconcile (or reset by fresh_rows_header); `types` and
+// sp.hs give the Statistics.db header.
+// ---------------------------------------------------------------------------
+struct OutputOptions {
+    std::string base;  // <dir>/<version>-<generation>-<format>
+    bool snappy = false, bti = false;
+    uint32_t chunk_len = CHUNK_LEN;
+    int wslot = 0;  // pinned-arena set (shards run two at a time)
+};
+
+// the one place OutStats becomes Statistics.db input (the rest of OutMeta —
+// key hashes, first/last key, tombstone histogram, ratio — is the caller's)
+static void fill_meta_from_stats(OutMeta& m, const OutStats& hst, const HeaderStats& hs,
+                                 const TableTypes& types) {
+    m.hdr_min_ts = hs.min_ts;
+    m.hdr_min_ldt = hs.min_ldt;
+    m.hdr_min_ttl = hs.min_ttl;
+    m.types = types;
+    const bool no_ts = hst.min_ts_flip == ~0ull;
+    m.min_timestamp = no_ts ? 0 : unflip(hst.min_ts_flip);
+    m.max_timestamp = no_ts ? 0 : unflip(hst.max_ts_flip);
+    m.min_ldt = unflip(hst.min_ldt_flip, ~0ull, NO_DELETION_TIME);
+    m.max_ldt = unflip(hst.max_ldt_flip, 0, 0);
+    m.min_ttl = hst.min_ttl == 0xFFFFFFFFu ? 0 : (int32_t)hst.min_ttl;
+    m.max_ttl = (int32_t)hst.max_ttl;
+    m.total_rows = hst.rows_out;
+    m.total_cells = hst.total_cells;
+    m.has_partition_deletions = hst.has_partition_deletions != 0;
+    memcpy(m.part_size_hist, hst.part_size_hist, sizeof(m.part_size_hist));
+    memcpy(m.cells_hist, hst.cells_hist, sizeof(m.cells_hist));
+}
+
 static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfColsBuf& rows,
                                            uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
                                            DevBuf& d_tomb, uint32_t tomb_cap,
-                                           const std::string& out_base,
-                                           const std::string& key_type,
-                                           const std::vector<std::string>& ck_types,
-                                           const std::vector<std::pair<bytes, std::string>>& regular_cols,
-                                           const std::vector<std::pair<bytes, std::string>>& static_cols,
-                                           hipStream_t stream, int wslot = 0,
-                                           bool snappy_out = false, bool bti_out = false,
-                                           uint32_t out_chunk_len = CHUNK_LEN) {
+                                           const TableTypes& types, const OutputOptions& opt,
+                                           hipStream_t stream) {
     WriteDeviceOut w;
-    if (!chunk_len_supported(out_chunk_len))
-        throw unsupported_error("unsupported output chunk_length " + std::to_string(out_chunk_len) +
+    if (!chunk_len_supported(opt.chunk_len))
+        throw unsupported_error("unsupported output chunk_length " + std::to_string(opt.chunk_len) +
                                 CHUNK_LEN_WHY);
-    const uint32_t OCL = out_chunk_len;
+    const std::string& out_base = opt.base;
+    const bool snappy_out = opt.snappy, bti_out = opt.bti;
+    const int wslot = opt.wslot;
+    const uint32_t OCL = opt.chunk_len;
     const uint32_t SLOT_STRIDE = snappy_out ? snp_slot_stride(OCL) : lz4_slot_stride(OCL);
     TR("wsd: enter");
     static const std::vector<int64_t> ps_off_h = est_hist_offsets(155);
@@ -1064,6 +813,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     Stream cstream;
     Event ev0, ev1, ev2, ev3, ev4;
 
+    // ==== stage 1: size and scan ====
     // ---- collect stats (needed before bloom sizing) ----
     {
         uint64_t blocks = (n_groups + 255) / 256;
@@ -1104,7 +854,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     w.rows = hst.rows_out;
     w.cells = hst.total_cells;
 
-    // ---- serialize (+ index + bloom) ----
+    // ==== stage 2: serialize (+ index + bloom) interleaved with compress ====
     HBloomSpec bs = bloom_spec_001();
     uint64_t num_bits = w.partitions * (uint64_t)bs.buckets + 20;
     uint64_t words = num_bits ? ((num_bits - 1) >> 6) + 1 : 1;
@@ -1215,12 +965,9 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     HIP_CHECK(hipEventRecord(ev3, stream));  // ev2..ev3: compress (+interleaved serialize) GPU time
     TR("wsd: compress issued");
 
+    // ==== stage 3: slab drain ====
     std::string data_path = out_base + "-Data.db";
-    {   // create/truncate so writers can pwrite into it
-        FILE* f = fopen(data_path.c_str(), "wb");
-        if (!f) throw std::runtime_error("cannot create " + data_path);
-        fclose(f);
-    }
+    write_file(data_path, nullptr, 0);  // create/truncate so writers can pwrite into it
     const uint64_t worst_slab = (uint64_t)SLAB * ((uint64_t)SLOT_STRIDE + 4);
     const int NSLOTS = 4;
     uint8_t* h_slab0 = (uint8_t*)g_pin_out[wslot][0].get(worst_slab * NSLOTS);
@@ -1275,26 +1022,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         tw_d2h += wallm() - tq2;
         uint64_t off0 = file_off;
         wfut[slot] = std::async(std::launch::async, [=]() {
-            int nth = 4;  // page-cache pwrites peak at ~4 threads (tools/wbench.c matrix)
-            std::vector<std::thread> th;
-            size_t per = (slab_bytes + nth - 1) / nth;
-            for (int t = 0; t < nth; t++) {
-                size_t o = (size_t)t * per;
-                if (o >= slab_bytes) break;
-                size_t len = std::min<size_t>(per, slab_bytes - o);
-                th.emplace_back([=]() {
-                    int fd = open(data_path.c_str(), O_WRONLY);
-                    if (fd < 0) return;
-                    size_t done = 0;
-                    while (done < len) {
-                        ssize_t ww = pwrite(fd, hbuf + o + done, len - done, (off_t)(off0 + o + done));
-                        if (ww <= 0) break;
-                        done += (size_t)ww;
-                    }
-                    close(fd);
-                });
-            }
-            for (auto& x : th) x.join();
+            pwrite_range(data_path, hbuf, slab_bytes, off0, 4);
         });
         file_off += slab_bytes;
     }
@@ -1323,6 +1051,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     }
     HIP_CHECK(hipEventRecord(ev4, stream));
 
+    // ==== stage 4: component tail (bytes decided in sstable_out.h) ====
     {
         std::vector<uint8_t> h_bloom(words * 8);
         std::vector<uint32_t> h_crc(n_chunks);
@@ -1336,98 +1065,12 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         TR("wsd: tail synced");
         // digest fold and the Summary.db index walk are independent of the
         // meta build: run all three concurrently (tail was serial: ~145 ms)
-        static Crc32Combiner comb;
-        std::future<uint32_t> fut_digest = std::async(std::launch::async, [&]() {
-            int nth = n_chunks > 4096 ? 16 : 1;
-            std::vector<uint32_t> pcrc(nth, 0);
-            std::vector<uint64_t> plen(nth, 0);
-            uint32_t per = (n_chunks + nth - 1) / nth;
-            std::vector<std::thread> th;
-            for (int t = 0; t < nth; t++) {
-                th.emplace_back([&, t]() {
-                    uint32_t c0 = t * per, c1 = std::min(n_chunks, (t + 1) * per);
-                    uint32_t d = 0;
-                    uint64_t l = 0;
-                    for (uint32_t c = c0; c < c1; c++) {
-                        d = comb.combine(d, h_crc[c], cs[c]);
-                        uint8_t cb2[4] = {(uint8_t)(h_crc[c] >> 24), (uint8_t)(h_crc[c] >> 16),
-                                          (uint8_t)(h_crc[c] >> 8), (uint8_t)h_crc[c]};
-                        d = comb.combine(d, crc32_update_bitwise(0, cb2, 4), 4);
-                        l += cs[c] + 4;
-                    }
-                    pcrc[t] = d;
-                    plen[t] = l;
-                });
-            }
-            for (auto& x : th) x.join();
-            uint32_t dg = 0;
-            for (int t = 0; t < nth; t++) dg = comb.combine(dg, pcrc[t], plen[t]);
-            return dg;
-        });
-
+        std::future<uint32_t> fut_digest =
+            std::async(std::launch::async, [&]() { return fold_digest(h_crc, cs); });
         std::future<bytes> fut_summary;
         if (!bti_out)
-            fut_summary = std::async(std::launch::async, [&]() -> bytes {
-            // IndexSummary at BASE_SAMPLING_LEVEL (IndexSummaryBuilder
-            // with empty Downsampling start points: entries for keys
-            // 0, 128, 256, ...), serialized per
-            // IndexSummary.IndexSummarySerializer.serialize — BE header,
-            // then the off-heap image in NATIVE (LE) order: rebased
-            // int offsets, then key bytes + LE u64 Index.db position;
-            // trailing first/last key with BE lengths
-            // (SSTableReader.saveSummary). Fixture-pinned by the
-            // oracle roundtrip of all four legacy_oa tables.
-            const uint32_t MIN_INTERVAL = 128;
-            bytes entries, s;
-            std::vector<uint32_t> offs;
-            const uint8_t *first_k = nullptr, *last_k = nullptr;
-            uint32_t first_kl = 0, last_kl = 0;
-            uint64_t q = 0, part_i = 0;
-            while (q < total_idx) {
-                uint64_t entry_off = q;
-                uint32_t klen = ((uint32_t)h_index[q] << 8) | h_index[q + 1];
-                const uint8_t* kp = h_index + q + 2;
-                q += 2 + klen;
-                if (!first_k) { first_k = kp; first_kl = klen; }
-                last_k = kp; last_kl = klen;
-                if (part_i % MIN_INTERVAL == 0) {
-                    offs.push_back((uint32_t)entries.size());
-                    entries.insert(entries.end(), kp, kp + klen);
-                    for (int b = 0; b < 8; b++) entries.push_back((uint8_t)(entry_off >> (8 * b)));
-                }
-                // skip position + promoted-index payload vints
-                auto skip_uvint = [&]() -> uint64_t {
-                    uint8_t f2 = h_index[q++];
-                    int extra = 0;
-                    uint8_t x = f2;
-                    while (x & 0x80) { extra++; x <<= 1; }
-                    uint64_t r2 = f2 & (uint8_t)(0xFFu >> extra);
-                    for (int i2 = 0; i2 < extra; i2++) r2 = (r2 << 8) | h_index[q++];
-                    return r2;
-                };
-                (void)skip_uvint();
-                q += skip_uvint();
-                part_i++;
-            }
-            uint32_t cnt = (uint32_t)offs.size();
-            put_be32(s, MIN_INTERVAL);
-            put_be32(s, cnt);
-            put_be64(s, 4ull * cnt + entries.size());
-            put_be32(s, 128);
-            put_be32(s, cnt);
-            for (uint32_t o : offs) {
-                uint32_t v = o + 4 * cnt;
-                for (int b = 0; b < 4; b++) s.push_back((uint8_t)(v >> (8 * b)));
-            }
-            s.insert(s.end(), entries.begin(), entries.end());
-            if (first_k) {
-                put_be32(s, first_kl);
-                s.insert(s.end(), first_k, first_k + first_kl);
-                put_be32(s, last_kl);
-                s.insert(s.end(), last_k, last_k + last_kl);
-            }
-            return s;
-            });
+            fut_summary = std::async(std::launch::async,
+                                     [&]() { return summary_db(h_index, total_idx); });
 
         std::vector<uint32_t> tombs;
         if (hst.tomb_count) {
@@ -1458,25 +1101,8 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
             for (uint64_t g2 = 0; g2 < n_groups; g2++)
                 if (keep[g2]) m.key_hashes.push_back(kh[g2]);
         }
-        m.hs = sp.hs;
-        m.key_type = key_type;
-        m.ck_types = ck_types;
-        m.regular_cols = regular_cols;
-        m.static_cols = static_cols;
-        bool no_ts = hst.min_ts_flip == 0xFFFFFFFFFFFFFFFFULL;
-        m.min_timestamp = no_ts ? 0 : (int64_t)(hst.min_ts_flip ^ 0x8000000000000000ULL);
-        m.max_timestamp = no_ts ? 0 : (int64_t)(hst.max_ts_flip ^ 0x8000000000000000ULL);
-        m.min_ldt = hst.min_ldt_flip == 0xFFFFFFFFFFFFFFFFULL ? NO_DELETION_TIME
-                                                              : (int64_t)(hst.min_ldt_flip ^ 0x8000000000000000ULL);
-        m.max_ldt = hst.max_ldt_flip == 0 ? 0 : (int64_t)(hst.max_ldt_flip ^ 0x8000000000000000ULL);
-        m.min_ttl = hst.min_ttl == 0xFFFFFFFFu ? 0 : (int32_t)hst.min_ttl;
-        m.max_ttl = (int32_t)hst.max_ttl;
-        m.total_rows = hst.rows_out;
-        m.total_cells = hst.total_cells;
-        m.has_partition_deletions = hst.has_partition_deletions != 0;
+        fill_meta_from_stats(m, hst, sp.hs, types);
         for (uint32_t tv : tombs) m.tomb_hist[tv]++;
-        memcpy(m.part_size_hist, hst.part_size_hist, sizeof(m.part_size_hist));
-        memcpy(m.cells_hist, hst.cells_hist, sizeof(m.cells_hist));
         m.compression_ratio = total_unc ? (double)(w.compressed_len - (uint64_t)n_chunks * 4) / (double)total_unc : -1.0;
         if (w.partitions) {
             uint64_t fg = hst.first_group, lg = hst.last_group;
@@ -1501,57 +1127,21 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         clock_gettime(CLOCK_MONOTONIC, &ts0);
         if (bti_out) {
             bti::bytes parts_img, rows_img;
-            std::vector<int32_t> ckw_h2;
-            for (auto& t2 : ck_types)
-                ckw_h2.push_back(t2 == "org.apache.cassandra.db.marshal.LongType" ? 8
-                                 : t2 == "org.apache.cassandra.db.marshal.Int32Type" ? 4
-                                                                                     : -1);
-            build_bti_from_index_image(h_index, total_idx, total_unc, ckw_h2,
-                                       &parts_img, &rows_img);
-            write_file(out_base + "-Partitions.db", parts_img.data(), parts_img.size());
-            write_file(out_base + "-Rows.db", rows_img.data(), rows_img.size());
+            std::vector<int32_t> ckw;
+            for (auto& t : types.clustering_types) ckw.push_back(type_width(t));
+            build_bti_from_index_image(h_index, total_idx, total_unc, ckw, &parts_img, &rows_img);
+            write_file(out_base + "-Partitions.db", parts_img);
+            write_file(out_base + "-Rows.db", rows_img);
         } else {
             write_file_parallel(out_base + "-Index.db", h_index, total_idx, 4);
         }
-        {
-            bytes f;
-            put_be32(f, (uint32_t)bs.k);
-            put_be32(f, (uint32_t)words);
-            f.insert(f.end(), h_bloom.begin(), h_bloom.end());
-            write_file(out_base + "-Filter.db", f.data(), f.size());
-        }
-        {
-            bytes ci;
-            std::string algo = snappy_out ? "SnappyCompressor" : "LZ4Compressor";
-            put_be16(ci, (uint16_t)algo.size());
-            ci.insert(ci.end(), algo.begin(), algo.end());
-            put_be32(ci, 0);
-            put_be32(ci, OCL);
-            put_be32(ci, 0x7FFFFFFF);
-            put_be64(ci, total_unc);
-            put_be32(ci, n_chunks);
-            uint64_t acc2 = 0;
-            for (uint32_t i = 0; i < n_chunks; i++) { put_be64(ci, acc2 + (uint64_t)i * 4); acc2 += cs[i]; }
-            write_file(out_base + "-CompressionInfo.db", ci.data(), ci.size());
-        }
-        {
-            std::string d = std::to_string(digest);
-            write_file(out_base + "-Digest.crc32", (const uint8_t*)d.data(), d.size());
-        }
-        {
-            bytes st = serialize_statistics_out(m);
-            write_file(out_base + "-Statistics.db", st.data(), st.size());
-        }
-        {
-            if (!bti_out) {
-                bytes s = fut_summary.get();
-                write_file(out_base + "-Summary.db", s.data(), s.size());
-            }
-            std::string toc = bti_out
-                ? "Data.db\nStatistics.db\nDigest.crc32\nTOC.txt\nCompressionInfo.db\nFilter.db\nPartitions.db\nRows.db\n"
-                : "Data.db\nStatistics.db\nDigest.crc32\nTOC.txt\nCompressionInfo.db\nFilter.db\nIndex.db\nSummary.db\n";
-            write_file(out_base + "-TOC.txt", (const uint8_t*)toc.data(), toc.size());
-        }
+        write_file(out_base + "-Filter.db", filter_db(bs.k, h_bloom));
+        write_file(out_base + "-CompressionInfo.db",
+                   compression_info_db(snappy_out, OCL, total_unc, cs));
+        write_file(out_base + "-Digest.crc32", digest_text(digest));
+        write_file(out_base + "-Statistics.db", serialize_statistics_out(m));
+        if (!bti_out) write_file(out_base + "-Summary.db", fut_summary.get());
+        write_file(out_base + "-TOC.txt", toc_text(bti_out));
         clock_gettime(CLOCK_MONOTONIC, &ts1);
         TR("wsd: components written");
         // residual (non-overlapped) component writes + the Data.db drain tail
@@ -1587,6 +1177,23 @@ extern "C" int gpuc_device_count(void) {
 static void set_err(char* dst, size_t cap, const std::string& msg) {
     if (!dst || !cap) return;
     snprintf(dst, cap, "%s", msg.c_str());
+}
+// The exception-to-code ladder of the entry points that report through an
+// error buffer. gpuc_compact (cancellation, timing), gpuc_verify and
+// gpuc_compress_buffer map differently and spell their own.
+template <class F> static int abi_guard(char* err, size_t cap, F&& body) {
+    try {
+        return body();
+    } catch (const unsupported_error& e) {
+        set_err(err, cap, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const format_error& e) {
+        set_err(err, cap, e.what());
+        return GPUC_ERR_FORMAT;
+    } catch (const std::exception& e) {
+        set_err(err, cap, e.what());
+        return GPUC_ERR_INTERNAL;
+    }
 }
 
 struct CompactSetup {
@@ -1806,8 +1413,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         parse_input(parsed, d_srcs, (uint32_t)k, total_parts, d_recs_a, sch, d_error, d_rows_in,
                     false, stream);
         const ParsedCols& pc = parsed.pc;
-        const UnfColsBuf& in_rows = parsed.rows;
-        const uint64_t total_in_rows = parsed.total_rows, total_in_cpx = parsed.total_cpx;
+        const uint64_t total_in_cpx = parsed.total_cpx;
         HIP_CHECK(hipEventRecord(e3, stream));
         {
             unsigned long long err = read_dev_error(d_error, stream);
@@ -1843,25 +1449,9 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         TR("merge issued");
 
         // ---- group heads + starts ----
-        DevBuf d_head, d_gstart, d_ngroups;
-        d_head.alloc(data_parts * 8 + 8);
-        d_gstart.alloc(data_parts * 8 + 8);
-        d_ngroups.alloc(8);
-        {
-            uint32_t blocks = (uint32_t)((data_parts + 255) / 256);
-            hipLaunchKernelGGL(k_group_heads, dim3(blocks), dim3(256), 0, stream, d_sorted,
-                               data_parts, d_head.as<uint64_t>(), lut);
-        }
-        exscan_u64(d_head.as<uint64_t>(), data_parts, stream);
-        {
-            uint32_t blocks = (uint32_t)((data_parts + 255) / 256);
-            hipLaunchKernelGGL(k_group_starts2, dim3(blocks), dim3(256), 0, stream, d_sorted,
-                               data_parts, d_head.as<uint64_t>(), d_gstart.as<uint64_t>(),
-                               d_ngroups.as<uint64_t>(), lut);
-        }
-        uint64_t n_groups = 0;
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(&n_groups, d_ngroups.p, 8, hipMemcpyDeviceToHost));
+        Groups groups;
+        find_groups(groups, d_sorted, data_parts, lut, stream);
+        const uint64_t n_groups = groups.n;
         TR("groups known");
         check_cancel(job);
 
@@ -1872,54 +1462,27 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         // live at this scope, past the reconcile-phase sync.
         std::vector<uint32_t> bases(k);
         std::vector<int64_t> klo_h, khi_h, ov_lo_h, ov_hi_h, ov_ts_h;
-        DevBuf d_srcbases, d_group_rows;
+        DevBuf d_srcbases;
         {
             for (int s = 0; s < k; s++) bases[s] = srcs[s].rec_base;
             d_srcbases.alloc(k * 4);
             HIP_CHECK(hipMemcpyAsync(d_srcbases.p, bases.data(), k * 4, hipMemcpyHostToDevice, stream));
         }
-        d_group_rows.alloc(n_groups * 8);
-        {
-            uint32_t blocks = (uint32_t)((n_groups + 255) / 256);
-            hipLaunchKernelGGL(k_group_row_sums, dim3(blocks), dim3(256), 0, stream, d_sorted,
-                               d_gstart.as<uint64_t>(), n_groups, data_parts,
-                               d_srcbases.as<uint32_t>(), pc, d_group_rows.as<uint64_t>());
-        }
-        uint64_t total_out_rows = exscan_u64(d_group_rows.as<uint64_t>(), n_groups, stream);
+        scan_group_rows(groups, d_srcbases, pc, stream);
         TR("out rows scanned");
-        OutPartsBuf opb;
-        opb.alloc(n_groups, sch.n_static);
-        UnfColsBuf out_rows;
-        out_rows.alloc(total_out_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
-        if (sch.n_cpx) out_rows.alloc_cpx_arena(total_in_cpx);
-        DevBuf d_stats, d_tomb;
-        d_stats.alloc(sizeof(OutStats));
-        init_outstats(d_stats, stream);
-        DevBuf d_ctr_arena;
+        Reconciled rec;
+        rec.alloc(groups, sch, total_in_cpx, stream);
+        OutPartsBuf& opb = rec.parts;
+        UnfColsBuf& out_rows = rec.rows;
+        DevBuf& d_stats = rec.stats;
+        DevBuf d_tomb, d_ctr_arena;
         uint64_t ctr_arena_cap = 0;
         if (sch.counters) {
-            // merged-context arena: capacity = total input counter bytes
-            // (any k-way merge result is bounded by the sum of its inputs)
-            DevBuf d_sum;
-            d_sum.alloc(8);
-            HIP_CHECK(hipMemsetAsync(d_sum.p, 0, 8, stream));
-            uint64_t n_cells = total_in_rows * sch.n_cols;
-            if (n_cells) {
-                uint32_t blocks2 = (uint32_t)((n_cells + 255) / 256);
-                hipLaunchKernelGGL(k_sum_vallen, dim3(blocks2), dim3(256), 0, stream,
-                                   in_rows.uc, n_cells, d_sum.as<unsigned long long>());
-            }
-            unsigned long long total_ctr = 0;
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(&total_ctr, d_sum.p, 8, hipMemcpyDeviceToHost));
-            ctr_arena_cap = total_ctr + 64;
+            ctr_arena_cap = counter_arena_cap(parsed, sch.n_cols, stream);
             d_ctr_arena.alloc(ctr_arena_cap);
             sch.ctr_arena = d_ctr_arena.as<uint8_t>();
         }
-        uint32_t tomb_cap = (uint32_t)std::min<uint64_t>(
-            total_out_rows * ((uint64_t)sch.n_cols + sch.n_cpx + 2) + total_in_cpx +
-                n_groups * ((uint64_t)sch.n_static + 2) + 1024,
-            400000000ull);
+        uint32_t tomb_cap = tomb_list_cap(groups.total_rows, total_in_cpx, n_groups, sch);
         d_tomb.alloc((uint64_t)tomb_cap * 4);
         DevBuf d_ov_lo, d_ov_hi, d_ov_ts;
         PurgeParams2 pp{};
@@ -2025,19 +1588,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             pp_data.never_purge = 1;
             pp_data.enforce_strict_liveness = 0;
         }
-        {
-            uint32_t blocks = (uint32_t)((n_groups + 255) / 256);
-            auto launch_rec = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, d_sorted,
-                                   d_gstart.as<uint64_t>(), n_groups, data_parts,
-                                   d_srcbases.as<uint32_t>(), pc, in_rows.uc, opb.op, out_rows.uc,
-                                   d_group_rows.as<uint64_t>(), sch, pp_data, d_stats.as<OutStats>(),
-                                   d_error.as<unsigned long long>());
-            };
-            if (kd <= 8) launch_rec(k_reconcile_rows<8>);
-            else if (kd <= 16) launch_rec(k_reconcile_rows<16>);
-            else launch_rec(k_reconcile_rows<64>);
-        }
+        launch_reconcile(groups, kd, d_srcbases, parsed, rec, sch, pp_data, d_error, stream);
         HIP_CHECK(hipEventRecord(er1, stream));
         HIP_CHECK(hipEventRecord(e4, stream));
         TR("reconcile issued");
@@ -2047,12 +1598,11 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         // ---- garbage collect: merge the tombstone sources, filter, purge ----
         UnfColsBuf gc_rows;          // filtered data arena (replaces out_rows)
         UnfColsBuf* rows_for_writer = &out_rows;
-        OutPartsBuf opb_t;
-        UnfColsBuf out_rows_t;
+        Groups groups_t;     // tombstone sources, reconciled among themselves
+        Reconciled rec_t;
         DevBuf d_ctr_arena_t;
         if (gc_mode && n_groups > 0) {
             uint64_t src_parts = total_parts - data_parts;
-            uint64_t n_groups_t = 0;
             if (src_parts > 0) {
                 std::vector<uint64_t> runs_t;
                 runs_t.push_back(0);
@@ -2060,33 +1610,9 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 MRec* d_sorted_t = merge_sorted_runs(d_recs_a.as<MRec>() + data_parts,
                                                      d_recs_b.as<MRec>() + data_parts, runs_t,
                                                      stream, lut);
-                DevBuf d_head_t, d_gstart_t, d_ng_t;
-                d_head_t.alloc(src_parts * 8 + 8);
-                d_gstart_t.alloc(src_parts * 8 + 8);
-                d_ng_t.alloc(8);
-                uint32_t blocks_t = (uint32_t)((src_parts + 255) / 256);
-                hipLaunchKernelGGL(k_group_heads, dim3(blocks_t), dim3(256), 0, stream, d_sorted_t,
-                                   src_parts, d_head_t.as<uint64_t>(), lut);
-                exscan_u64(d_head_t.as<uint64_t>(), src_parts, stream);
-                hipLaunchKernelGGL(k_group_starts2, dim3(blocks_t), dim3(256), 0, stream, d_sorted_t,
-                                   src_parts, d_head_t.as<uint64_t>(), d_gstart_t.as<uint64_t>(),
-                                   d_ng_t.as<uint64_t>(), lut);
-                HIP_CHECK(hipStreamSynchronize(stream));
-                HIP_CHECK(hipMemcpy(&n_groups_t, d_ng_t.p, 8, hipMemcpyDeviceToHost));
-                DevBuf d_grows_t, d_stats_t;
-                d_grows_t.alloc(n_groups_t * 8 + 8);
-                {
-                    uint32_t blocks_g = (uint32_t)((n_groups_t + 255) / 256);
-                    hipLaunchKernelGGL(k_group_row_sums, dim3(blocks_g), dim3(256), 0, stream,
-                                       d_sorted_t, d_gstart_t.as<uint64_t>(), n_groups_t, src_parts,
-                                       d_srcbases.as<uint32_t>(), pc, d_grows_t.as<uint64_t>());
-                }
-                uint64_t t_out_rows = exscan_u64(d_grows_t.as<uint64_t>(), n_groups_t, stream);
-                opb_t.alloc(n_groups_t ? n_groups_t : 1, sch.n_static);
-                out_rows_t.alloc(t_out_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
-                if (sch.n_cpx) out_rows_t.alloc_cpx_arena(total_in_cpx);
-                d_stats_t.alloc(sizeof(OutStats));
-                init_outstats(d_stats_t, stream);
+                find_groups(groups_t, d_sorted_t, src_parts, lut, stream);
+                scan_group_rows(groups_t, d_srcbases, pc, stream);
+                rec_t.alloc(groups_t, sch, total_in_cpx, stream);
                 // the source pass bump-allocates merged counter contexts from
                 // its own arena (the main pass's bump counter lives in the
                 // OTHER OutStats, so sharing one arena would overlap)
@@ -2097,22 +1623,12 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 }
                 PurgeParams2 pp_src = pp_data;
                 pp_src.has_shard = 0;  // sources shadow regardless of the shard
-                {
-                    uint32_t blocks_g = (uint32_t)((n_groups_t + 255) / 256);
-                    auto launch_rec_t = [&](auto kern) {
-                        hipLaunchKernelGGL(kern, dim3(blocks_g), dim3(256), 0, stream, d_sorted_t,
-                                           d_gstart_t.as<uint64_t>(), n_groups_t, src_parts,
-                                           d_srcbases.as<uint32_t>(), pc, in_rows.uc, opb_t.op,
-                                           out_rows_t.uc, d_grows_t.as<uint64_t>(), sch_t, pp_src,
-                                           d_stats_t.as<OutStats>(),
-                                           d_error.as<unsigned long long>());
-                    };
-                    int ks = k - kd;
-                    if (ks <= 8) launch_rec_t(k_reconcile_rows<8>);
-                    else if (ks <= 16) launch_rec_t(k_reconcile_rows<16>);
-                    else launch_rec_t(k_reconcile_rows<64>);
-                }
+                launch_reconcile(groups_t, k - kd, d_srcbases, parsed, rec_t, sch_t, pp_src,
+                                 d_error, stream);
             }
+            const OutPartsBuf& opb_t = rec_t.parts;
+            const UnfColsBuf& out_rows_t = rec_t.rows;
+            const uint64_t n_groups_t = groups_t.n;
             // match + capacity scan + filter
             DevBuf d_tidx, d_cap;
             d_tidx.alloc(n_groups * 8);
@@ -2227,11 +1743,9 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             }
             return;
         }
-        WriteDeviceOut w = write_sstable_device(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
-                                                tomb_cap, out_base_str, stats[0].key_type,
-                                                stats[0].clustering_types, stats[0].regular_cols,
-                                                stats[0].static_cols, stream, wslot,
-                                                su.cinfos[0].snappy, su.bti, su.out_chunk_len);
+        WriteDeviceOut w = write_sstable_device(
+            opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb, tomb_cap, stats[0],
+            OutputOptions{out_base_str, su.cinfos[0].snappy, su.bti, su.out_chunk_len, wslot}, stream);
         TR("writer done");
         {
             OutStats hst;
@@ -2658,21 +2172,16 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
 
         // digest from the chunk frames (CRC fields validated against bytes below)
         {
-            static Crc32Combiner comb;
-            uint32_t tab[256];
-            crc32_make_table(tab);
-            uint32_t digest = 0;
+            std::vector<uint32_t> crcs, sizes;
             for (const ChunkFrame& fr : frames) {
-                uint64_t blen = fr.comp_len;
-                uint64_t end = fr.off + blen + 4;
-                uint32_t ccrc = ((uint32_t)comp[end - 4] << 24) | ((uint32_t)comp[end - 3] << 16) |
-                                ((uint32_t)comp[end - 2] << 8) | comp[end - 1];
-                digest = comb.combine(digest, ccrc, blen);
-                digest = comb.combine(digest, crc32_update_t(0, comp.data() + end - 4, 4, tab), 4);
+                const uint8_t* p = comp.data() + fr.off + fr.comp_len;
+                crcs.push_back(((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) |
+                               ((uint32_t)p[2] << 8) | p[3]);
+                sizes.push_back(fr.comp_len);
             }
             bytes dg = read_file(base + "-Digest.crc32");
             std::string want(dg.begin(), dg.end());
-            if (want != std::to_string(digest))
+            if (want != digest_text(fold_digest(crcs, sizes)))
                 throw std::runtime_error("Digest.crc32 mismatch");
         }
 
@@ -2761,7 +2270,7 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
 // standard writer; report kept/dropped counts.
 extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32_t device,
                           uint64_t* kept, uint64_t* dropped, char* error, size_t error_len) {
-    try {
+    return abi_guard(error, error_len, [&]() -> int {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         HIP_CHECK(hipSetDevice(device));
         Stream stream;
@@ -2839,10 +2348,6 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
         ParsedInput parsed;
         parse_input(parsed, d_src, 1u, n_kept, d_recs, sch, d_error, d_rows_in, false, stream);
-        const ParsedCols& pc = parsed.pc;
-        const UnfColsBuf& in_rows = parsed.rows;
-        const uint64_t total_rows = parsed.total_rows, total_in_cpx = parsed.total_cpx;
-        const uint32_t blocks = (uint32_t)((n_kept + 255) / 256);
         if (unsigned long long e = read_dev_error(d_error, stream))
             throw std::runtime_error("scrub parse failed, code " + std::to_string(e));
         // single source: records are already in DecoratedKey order
@@ -2850,76 +2355,27 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         lut.base[0] = d_data.as<uint8_t>();
         lut.pos[0] = d_kpos.as<uint64_t>();
         lut.enabled = 1;
-        DevBuf d_head, d_gstart, d_ng;
-        d_head.alloc(n_kept * 8 + 8);
-        d_gstart.alloc(n_kept * 8 + 8);
-        d_ng.alloc(8);
-        HIP_CHECK(hipMemsetAsync(d_ng.p, 0, 8, stream));
-        if (n_kept) {
-            hipLaunchKernelGGL(k_group_heads, dim3(blocks), dim3(256), 0, stream, d_recs.as<MRec>(),
-                               n_kept, d_head.as<uint64_t>(), lut);
-            exscan_u64(d_head.as<uint64_t>(), n_kept, stream);
-            hipLaunchKernelGGL(k_group_starts2, dim3(blocks), dim3(256), 0, stream,
-                               d_recs.as<MRec>(), n_kept, d_head.as<uint64_t>(),
-                               d_gstart.as<uint64_t>(), d_ng.as<uint64_t>(), lut);
-        }
-        uint64_t n_groups = 0;
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(&n_groups, d_ng.p, 8, hipMemcpyDeviceToHost));
-        DevBuf d_srcbases, d_grows, d_stats, d_tomb;
+        Groups groups;
+        find_groups(groups, d_recs.as<MRec>(), n_kept, lut, stream);
+        DevBuf d_srcbases, d_tomb;
         uint32_t zero = 0;
         d_srcbases.alloc(8);
         HIP_CHECK(hipMemcpyAsync(d_srcbases.p, &zero, 4, hipMemcpyHostToDevice, stream));
-        d_grows.alloc(n_groups * 8 + 8);
-        if (n_groups) {
-            uint32_t gblocks = (uint32_t)((n_groups + 255) / 256);
-            hipLaunchKernelGGL(k_group_row_sums, dim3(gblocks), dim3(256), 0, stream,
-                               d_recs.as<MRec>(), d_gstart.as<uint64_t>(), n_groups, n_kept,
-                               d_srcbases.as<uint32_t>(), pc, d_grows.as<uint64_t>());
-        }
-        uint64_t out_total = n_groups ? exscan_u64(d_grows.as<uint64_t>(), n_groups, stream) : 0;
-        OutPartsBuf opb;
-        opb.alloc(n_groups ? n_groups : 1, sch.n_static);
-        UnfColsBuf out_rows;
-        out_rows.alloc(out_total, sch.n_cols, sch.n_ck, sch.n_cpx);
-        if (sch.n_cpx) out_rows.alloc_cpx_arena(total_in_cpx);
-        DevBuf d_ctr_arena_s;
+        scan_group_rows(groups, d_srcbases, parsed.pc, stream);
+        Reconciled rec;
+        rec.alloc(groups, sch, parsed.total_cpx, stream);
+        DevBuf d_ctr_arena;
         if (sch.counters) {
-            // merged-context arena (arity-1 reconcile still routes counter
-            // cells through the context branch)
-            DevBuf d_sum;
-            d_sum.alloc(8);
-            HIP_CHECK(hipMemsetAsync(d_sum.p, 0, 8, stream));
-            uint64_t n_cells = total_rows * sch.n_cols;
-            if (n_cells) {
-                uint32_t blocks2 = (uint32_t)((n_cells + 255) / 256);
-                hipLaunchKernelGGL(k_sum_vallen, dim3(blocks2), dim3(256), 0, stream,
-                                   in_rows.uc, n_cells, d_sum.as<unsigned long long>());
-            }
-            unsigned long long total_ctr = 0;
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(&total_ctr, d_sum.p, 8, hipMemcpyDeviceToHost));
-            d_ctr_arena_s.alloc(total_ctr + 64);
-            sch.ctr_arena = d_ctr_arena_s.as<uint8_t>();
+            // arity-1 reconcile still routes counter cells through the context branch
+            d_ctr_arena.alloc(counter_arena_cap(parsed, sch.n_cols, stream));
+            sch.ctr_arena = d_ctr_arena.as<uint8_t>();
         }
-        d_stats.alloc(sizeof(OutStats));
-        init_outstats(d_stats, stream);
-        uint32_t tomb_cap = (uint32_t)std::min<uint64_t>(
-            out_total * ((uint64_t)sch.n_cols + sch.n_cpx + 2) + total_in_cpx +
-                n_groups * ((uint64_t)sch.n_static + 2) + 1024,
-            400000000ull);
+        uint32_t tomb_cap = tomb_list_cap(groups.total_rows, parsed.total_cpx, groups.n, sch);
         d_tomb.alloc((uint64_t)tomb_cap * 4);
         PurgeParams2 pp{};
         pp.gc_before = INT64_MIN;
         pp.never_purge = 1;
-        if (n_groups) {
-            uint32_t gblocks = (uint32_t)((n_groups + 255) / 256);
-            hipLaunchKernelGGL(k_reconcile_rows<8>, dim3(gblocks), dim3(256), 0, stream,
-                               d_recs.as<MRec>(), d_gstart.as<uint64_t>(), n_groups, n_kept,
-                               d_srcbases.as<uint32_t>(), pc, in_rows.uc, opb.op, out_rows.uc,
-                               d_grows.as<uint64_t>(), sch, pp, d_stats.as<OutStats>(),
-                               d_error.as<unsigned long long>());
-        }
+        launch_reconcile(groups, 1, d_srcbases, parsed, rec, sch, pp, d_error, stream);
         if (unsigned long long e = read_dev_error(d_error, stream))
             throw std::runtime_error("scrub reconcile failed, code " + std::to_string(e));
         SerParams2 sp2{};
@@ -2927,20 +2383,10 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         sp2.hs.min_ts = st.min_timestamp == NO_TIMESTAMP ? TIMESTAMP_EPOCH : st.min_timestamp;
         sp2.hs.min_ldt = st.min_ldt == NO_DELETION_TIME ? DELETION_TIME_EPOCH : st.min_ldt;
         sp2.hs.min_ttl = st.min_ttl == INT32_MAX ? 0 : st.min_ttl;
-        write_sstable_device(opb, out_rows, n_groups, sp2, d_stats, d_tomb, tomb_cap, output_base,
-                             st.key_type, st.clustering_types, st.regular_cols, st.static_cols,
-                             stream, 0, ci.snappy, false, ci.chunk_len);
+        write_sstable_device(rec.parts, rec.rows, groups.n, sp2, rec.stats, d_tomb, tomb_cap, st,
+                             OutputOptions{output_base, ci.snappy, false, ci.chunk_len, 0}, stream);
         return GPUC_OK;
-    } catch (const unsupported_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_UNSUPPORTED;
-    } catch (const format_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_FORMAT;
-    } catch (const std::exception& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_INTERNAL;
-    }
+    });
 }
 
 // Memtable flush: unsorted unique-key rows from the host ->
@@ -2949,7 +2395,7 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
 // (one regular column; row tombstones via del_ldt != UINT32_MAX).
 extern "C" int gpuc_flush(const gpuc_flush_rows* rows, const char* output_base,
                           int32_t device, char* error, size_t error_len) {
-    try {
+    return abi_guard(error, error_len, [&]() -> int {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         if (!rows || rows->n_rows == 0) { set_err(error, error_len, "no rows"); return GPUC_ERR_UNSUPPORTED; }
         HIP_CHECK(hipSetDevice(device));
@@ -3026,58 +2472,25 @@ extern "C" int gpuc_flush(const gpuc_flush_rows* rows, const char* output_base,
             HIP_CHECK(hipMemcpy(&e, d_err.p, 8, hipMemcpyDeviceToHost));
             if (e == 40) throw std::runtime_error("duplicate partition keys in flush input");
         }
-        // header mins (SerializationHeader.make at flush: collect, then write)
+        // header mins (SerializationHeader.make at flush: collect, then write).
+        // k_flush_fill writes no TTL (live_ttl and every cell_ttl are 0), so
+        // the collected min_ttl is never folded into and decodes to 0.
         DevBuf d_stats, d_tomb;
-        d_stats.alloc(sizeof(OutStats));
-        init_outstats(d_stats, stream);
         uint32_t tomb_cap = (uint32_t)std::min<uint64_t>(n * 3 + 1024, 400000000ull);
-        d_tomb.alloc((uint64_t)tomb_cap * 4);
-        hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op,
-                           urows.uc, n, 1u, 0u, d_stats.as<OutStats>(), d_tomb.as<uint32_t>(),
-                           tomb_cap);
-        OutStats hs0;
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(&hs0, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
         SerParams2 sp{};
-        sp.hs.min_ts = hs0.min_ts_flip == 0xFFFFFFFFFFFFFFFFULL
-                           ? TIMESTAMP_EPOCH : (int64_t)(hs0.min_ts_flip ^ 0x8000000000000000ULL);
-        sp.hs.min_ldt = hs0.min_ldt_flip == 0xFFFFFFFFFFFFFFFFULL
-                            ? DELETION_TIME_EPOCH : (int64_t)(hs0.min_ldt_flip ^ 0x8000000000000000ULL);
-        if (sp.hs.min_ldt == NO_DELETION_TIME) sp.hs.min_ldt = DELETION_TIME_EPOCH;
-        sp.hs.min_ttl = 0;
-        sp.sch.n_ck = 0;
-        DevBuf d_ckw;
-        d_ckw.alloc(8);
-        sp.sch.ck_w = d_ckw.as<int32_t>();
-        sp.sch.n_cols = 1;
-        std::vector<int32_t> cf{-1};
-        DevBuf d_cf;
-        d_cf.alloc(8);
-        HIP_CHECK(hipMemcpyAsync(d_cf.p, cf.data(), 4, hipMemcpyHostToDevice, stream));
-        sp.sch.col_fixed = d_cf.as<int32_t>();
-        sp.sch.n_static = 0;
-        DevBuf d_sf;
-        d_sf.alloc(8);
-        sp.sch.static_fixed = d_sf.as<int32_t>();
-        sp.sch.column_index_size = 64 * 1024;
-        init_outstats(d_stats, stream);
-        std::vector<std::pair<bytes, std::string>> cols = {
-            {bytes{'v', 'a', 'l'}, "org.apache.cassandra.db.marshal.BytesType"}};
-        write_sstable_device(opb, urows, n, sp, d_stats, d_tomb, tomb_cap, output_base,
-                             "org.apache.cassandra.db.marshal.BytesType",
-                             std::vector<std::string>{}, cols,
-                             std::vector<std::pair<bytes, std::string>>{}, stream);
+        sp.hs = fresh_rows_header(opb, urows, n, 1u, 0u, d_stats, d_tomb, tomb_cap, stream);
+        HostSchema hsch;
+        hsch.col_fixed = {-1};  // val blob
+        DevSchema dsch;
+        sp.sch = dsch.upload(hsch, stream);
+        TableTypes types;
+        types.key_type = "org.apache.cassandra.db.marshal.BytesType";
+        types.regular_cols = {{bytes{'v', 'a', 'l'}, "org.apache.cassandra.db.marshal.BytesType"}};
+        OutputOptions opt;
+        opt.base = output_base;
+        write_sstable_device(opb, urows, n, sp, d_stats, d_tomb, tomb_cap, types, opt, stream);
         return GPUC_OK;
-    } catch (const unsupported_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_UNSUPPORTED;
-    } catch (const format_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_FORMAT;
-    } catch (const std::exception& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_INTERNAL;
-    }
+    });
 }
 
 
@@ -3160,7 +2573,7 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                                 uint64_t n_parts, const char* output_base, int32_t device,
                                 char* error, size_t error_len) {
     using namespace flushv2;
-    try {
+    return abi_guard(error, error_len, [&]() -> int {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         if (!schema || !parts || n_parts == 0) throw std::runtime_error("no partitions");
         const gpuc_flush_schema& S = *schema;
@@ -3171,38 +2584,38 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         if (S.n_ck > 32) throw std::runtime_error("at most 32 clustering columns");
         const std::string MAPT_PFX = "org.apache.cassandra.db.marshal.MapType";
         const std::string CTRT = "org.apache.cassandra.db.marshal.CounterColumnType";
-        std::string key_type = S.key_type ? S.key_type
-                                          : "org.apache.cassandra.db.marshal.BytesType";
-        std::vector<std::string> ck_types;
-        std::vector<int32_t> ckw_h;
+        // the types go to the Statistics.db header as given; the widths the
+        // kernels walk with: clustering types must be known (ck_type_width
+        // throws), an unknown regular or static type is variable width
+        TableTypes types;
+        HostSchema hsch;
+        types.key_type = S.key_type ? S.key_type : "org.apache.cassandra.db.marshal.BytesType";
         for (uint32_t i = 0; i < S.n_ck; i++) {
-            ck_types.emplace_back(S.ck_types[i]);
-            ckw_h.push_back(ck_type_width(ck_types.back()));
+            types.clustering_types.emplace_back(S.ck_types[i]);
+            hsch.ck_widths.push_back(ck_type_width(types.clustering_types.back()));
         }
+        const std::vector<int32_t>& ckw_h = hsch.ck_widths;
         // n_cols in the ABI counts ALL regular columns; SchemaParams.n_cols
         // counts the SIMPLE ones (the n_cpx complex ones last, excluded)
         const uint32_t NSIMPLE = S.n_cols - S.n_cpx;
         const uint32_t NX = S.n_cpx;
-        std::vector<std::pair<bytes, std::string>> regular_cols, static_cols;
-        std::vector<int32_t> colw_h, staticw_h;
-        bool counters = false;
+        hsch.n_cpx = S.n_cpx;
         for (uint32_t i = 0; i < S.n_cols; i++) {
             std::string t(S.col_types[i]);
             bool is_map = t.compare(0, MAPT_PFX.size(), MAPT_PFX) == 0;
             if (is_map != (i >= NSIMPLE))
                 throw std::runtime_error(
                     "the complex (MapType) columns must be the last n_cpx regular columns");
-            if (t == CTRT) counters = true;
-            regular_cols.emplace_back(bytes(S.col_names[i], S.col_names[i] + S.col_name_lens[i]), t);
-            if (i < NSIMPLE)
-                colw_h.push_back(t == "org.apache.cassandra.db.marshal.LongType" ? 8
-                                 : t == "org.apache.cassandra.db.marshal.Int32Type" ? 4 : -1);
+            if (t == CTRT) hsch.counters = true;
+            types.regular_cols.emplace_back(
+                bytes(S.col_names[i], S.col_names[i] + S.col_name_lens[i]), t);
+            if (i < NSIMPLE) hsch.col_fixed.push_back(type_width(t));
         }
         for (uint32_t i = 0; i < S.n_static; i++) {
             std::string t(S.static_types[i]);
-            static_cols.emplace_back(bytes(S.static_names[i], S.static_names[i] + S.static_name_lens[i]), t);
-            staticw_h.push_back(t == "org.apache.cassandra.db.marshal.LongType" ? 8
-                                : t == "org.apache.cassandra.db.marshal.Int32Type" ? 4 : -1);
+            types.static_cols.emplace_back(
+                bytes(S.static_names[i], S.static_names[i] + S.static_name_lens[i]), t);
+            hsch.static_fixed.push_back(type_width(t));
         }
         // ---- pass 0: totals + validation ----
         uint64_t key_bytes = 0, n_unf = 0, val_bytes = 0, cpx_total = 0;
@@ -3526,67 +2939,25 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
             }
         }
         // ---- header mins from a pre-collect (gpuc_generate's recipe) ----
-        DevBuf d_stats, d_tomb;
-        d_stats.alloc(sizeof(OutStats));
-        init_outstats(d_stats, stream);
-        uint32_t tomb_cap = (uint32_t)std::min<uint64_t>(
-            n_unf * ((uint64_t)NSIMPLE + S.n_cpx + 2) + cpx_total +
-                n_parts * ((uint64_t)S.n_static + 2) + 1024,
-            400000000ull);
-        d_tomb.alloc((uint64_t)tomb_cap * 4);
-        uint32_t blocks = (uint32_t)((n_parts + 255) / 256);
-        hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op, urows.uc,
-                           n_parts, NCV, NX, d_stats.as<OutStats>(), d_tomb.as<uint32_t>(),
-                           tomb_cap);
-        OutStats hs0;
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipMemcpy(&hs0, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
+        DevSchema dsch;
         SerParams2 sp{};
+        sp.sch = dsch.upload(hsch, stream,
+                             S.column_index_size ? S.column_index_size : 64 * 1024);
+        DevBuf d_stats, d_tomb;
+        uint32_t tomb_cap = tomb_list_cap(n_unf, cpx_total, n_parts, sp.sch);
+        sp.hs = fresh_rows_header(opb, urows, n_parts, NCV, NX, d_stats, d_tomb, tomb_cap, stream);
         if (S.has_stats) {
             // caller-provided EncodingStats (Memtable -> SerializationHeader.make)
             sp.hs.min_ts = S.stats_min_ts;
             sp.hs.min_ldt = S.stats_min_ldt;
             sp.hs.min_ttl = S.stats_min_ttl;
-        } else {
-            sp.hs.min_ts = hs0.min_ts_flip == 0xFFFFFFFFFFFFFFFFULL
-                               ? TIMESTAMP_EPOCH : (int64_t)(hs0.min_ts_flip ^ 0x8000000000000000ULL);
-            sp.hs.min_ldt = hs0.min_ldt_flip == 0xFFFFFFFFFFFFFFFFULL
-                                ? DELETION_TIME_EPOCH : (int64_t)(hs0.min_ldt_flip ^ 0x8000000000000000ULL);
-            if (sp.hs.min_ldt == NO_DELETION_TIME) sp.hs.min_ldt = DELETION_TIME_EPOCH;
-            sp.hs.min_ttl = hs0.min_ttl == 0xFFFFFFFFu ? 0 : (int32_t)hs0.min_ttl;
         }
-        sp.sch.n_ck = S.n_ck;
-        DevBuf d_ckw, d_cf2, d_sf2;
-        d_ckw.alloc(ckw_h.size() * 4 + 8);
-        if (S.n_ck) up(d_ckw, ckw_h.data(), ckw_h.size() * 4);
-        sp.sch.ck_w = d_ckw.as<int32_t>();
-        sp.sch.n_cols = NSIMPLE;
-        d_cf2.alloc(colw_h.size() * 4 + 8);
-        if (NSIMPLE) up(d_cf2, colw_h.data(), colw_h.size() * 4);
-        sp.sch.col_fixed = d_cf2.as<int32_t>();
-        sp.sch.n_static = S.n_static;
-        d_sf2.alloc(staticw_h.size() * 4 + 8);
-        if (S.n_static) up(d_sf2, staticw_h.data(), staticw_h.size() * 4);
-        sp.sch.static_fixed = d_sf2.as<int32_t>();
-        sp.sch.n_cpx = S.n_cpx;
-        sp.sch.counters = counters ? 1u : 0u;
-        sp.sch.column_index_size = S.column_index_size ? S.column_index_size : 64 * 1024;
-        init_outstats(d_stats, stream);
-        write_sstable_device(opb, urows, n_parts, sp, d_stats, d_tomb, tomb_cap, output_base,
-                             key_type, ck_types, regular_cols, static_cols, stream, 0,
-                             S.snappy != 0, S.bti != 0,
-                             checked_chunk_len_arg(S.chunk_length, CHUNK_LEN));
+        write_sstable_device(opb, urows, n_parts, sp, d_stats, d_tomb, tomb_cap, types,
+                             OutputOptions{output_base, S.snappy != 0, S.bti != 0,
+                                           checked_chunk_len_arg(S.chunk_length, CHUNK_LEN), 0},
+                             stream);
         return GPUC_OK;
-    } catch (const unsupported_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_UNSUPPORTED;
-    } catch (const format_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_FORMAT;
-    } catch (const std::exception& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_INTERNAL;
-    }
+    });
 }
 
 extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
@@ -3606,7 +2977,7 @@ extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t
 }
 
 extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* error, size_t error_len) {
-    try {
+    return abi_guard(error, error_len, [&]() -> int {
         if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
         (void)checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN);  // before any work
         HIP_CHECK(hipSetDevice(spec->device));
@@ -3709,59 +3080,23 @@ extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* e
             hipLaunchKernelGGL(k_gen_values2, dim3(blocks), dim3(256), 0, stream, gp, d_sorted,
                                d_ids.as<uint64_t>(), opb.op, rows.uc, R, d_vals.as<uint8_t>(),
                                d_prows.as<uint64_t>());
-            d_stats.alloc(sizeof(OutStats));
-            init_outstats(d_stats, stream);
+            // the generator's own bound: at most 7 cells per complex column
             uint32_t tomb_cap = (uint32_t)std::min<uint64_t>(
                 total_rows * ((uint64_t)gp.n_value_cols + (gp.complex_pct ? 7 : 0) + 2) +
                     R * 3 + 1024,
                 400000000ull);
-            d_tomb.alloc((uint64_t)tomb_cap * 4);
-            {
-                hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op,
-                                   rows.uc, R, gp.n_value_cols, gp.complex_pct ? 1u : 0u,
-                                   d_stats.as<OutStats>(),
-                                   d_tomb.as<uint32_t>(), tomb_cap);
-            }
-            OutStats hs0;
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(&hs0, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
             SerParams2 sp{};
-            sp.hs.min_ts = hs0.min_ts_flip == 0xFFFFFFFFFFFFFFFFULL
-                               ? TIMESTAMP_EPOCH : (int64_t)(hs0.min_ts_flip ^ 0x8000000000000000ULL);
-            sp.hs.min_ldt = hs0.min_ldt_flip == 0xFFFFFFFFFFFFFFFFULL
-                                ? DELETION_TIME_EPOCH : (int64_t)(hs0.min_ldt_flip ^ 0x8000000000000000ULL);
-            if (sp.hs.min_ldt == NO_DELETION_TIME) sp.hs.min_ldt = DELETION_TIME_EPOCH;
-            sp.hs.min_ttl = hs0.min_ttl == 0xFFFFFFFFu ? 0 : (int32_t)hs0.min_ttl;
-            sp.sch.n_ck = gen_nck;
-            std::vector<int32_t> ckw_h(gen_nck, gp.ck_text ? -1 : 8);
-            DevBuf d_ckw;
-            d_ckw.alloc(ckw_h.size() * 4 + 8);
-            if (gen_nck)
-                HIP_CHECK(hipMemcpyAsync(d_ckw.p, ckw_h.data(), ckw_h.size() * 4,
-                                         hipMemcpyHostToDevice, stream));
-            sp.sch.ck_w = d_ckw.as<int32_t>();
-            sp.sch.n_static = gp.static_pct ? 1 : 0;
-            std::vector<int32_t> sfx_h(1, -1);
-            DevBuf d_sfx;
-            d_sfx.alloc(8);
-            HIP_CHECK(hipMemcpyAsync(d_sfx.p, sfx_h.data(), 4, hipMemcpyHostToDevice, stream));
-            sp.sch.static_fixed = d_sfx.as<int32_t>();
-            sp.sch.n_cols = gp.n_value_cols;
-            sp.sch.n_cpx = gp.complex_pct ? 1 : 0;
-            std::vector<int32_t> gcf(gp.n_value_cols, -1);  // val blobs
-            DevBuf d_gcf;
-            d_gcf.alloc(gcf.size() * 4);
-            HIP_CHECK(hipMemcpyAsync(d_gcf.p, gcf.data(), gcf.size() * 4,
-                                     hipMemcpyHostToDevice, stream));
-            sp.sch.col_fixed = d_gcf.as<int32_t>();
-            sp.sch.column_index_size = 64 * 1024;
-            // reset and recollect so the writer sees fresh stats (collect ran
-            // once above only to derive the header mins)
-            init_outstats(d_stats, stream);
-            std::string base = spec->bti
-                ? std::string(dir) + "/da-" + std::to_string(spec->first_generation + s) + "-bti"
-                : std::string(dir) + "/oa-" + std::to_string(spec->first_generation + s) + "-big";
-            std::vector<std::pair<bytes, std::string>> cols;
+            sp.hs = fresh_rows_header(opb, rows, R, gp.n_value_cols, gp.complex_pct ? 1u : 0u,
+                                      d_stats, d_tomb, tomb_cap, stream);
+            HostSchema hsch;
+            hsch.ck_widths.assign(gen_nck, gp.ck_text ? -1 : 8);
+            hsch.col_fixed.assign(gp.n_value_cols, -1);          // val blobs
+            hsch.static_fixed.assign(gp.static_pct ? 1 : 0, -1);  // blob
+            hsch.n_cpx = gp.complex_pct ? 1 : 0;
+            DevSchema dsch;
+            sp.sch = dsch.upload(hsch, stream);
+            TableTypes types;
+            std::vector<std::pair<bytes, std::string>>& cols = types.regular_cols;
             if (gp.counter) {
                 cols.push_back({bytes{'c', 'n', 't'}, "org.apache.cassandra.db.marshal.CounterColumnType"});
             } else if (gp.n_value_cols == 1) {
@@ -3775,29 +3110,23 @@ extern "C" int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* e
             }
             if (gp.complex_pct)
                 cols.push_back({bytes{'z', 'm'}, "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,org.apache.cassandra.db.marshal.BytesType)"});
-            std::vector<std::pair<bytes, std::string>> scols;
             if (gp.static_pct)
-                scols.push_back({bytes{'s', '0'}, "org.apache.cassandra.db.marshal.BytesType"});
-            write_sstable_device(opb, rows, R, sp, d_stats, d_tomb, tomb_cap, base,
-                                 gp.key_len > 8 ? "org.apache.cassandra.db.marshal.BytesType"
-                                                : "org.apache.cassandra.db.marshal.LongType",
-                                 std::vector<std::string>(
-                                     gen_nck, gp.ck_text ? "org.apache.cassandra.db.marshal.UTF8Type"
-                                                         : "org.apache.cassandra.db.marshal.LongType"),
-                                 cols, scols, stream, 0, spec->snappy != 0, spec->bti != 0,
-                                 checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN));
+                types.static_cols.push_back({bytes{'s', '0'}, "org.apache.cassandra.db.marshal.BytesType"});
+            types.key_type = gp.key_len > 8 ? "org.apache.cassandra.db.marshal.BytesType"
+                                            : "org.apache.cassandra.db.marshal.LongType";
+            types.clustering_types.assign(gen_nck, gp.ck_text
+                                                       ? "org.apache.cassandra.db.marshal.UTF8Type"
+                                                       : "org.apache.cassandra.db.marshal.LongType");
+            OutputOptions opt;
+            opt.base = std::string(dir) + (spec->bti ? "/da-" : "/oa-") +
+                       std::to_string(spec->first_generation + s) + (spec->bti ? "-bti" : "-big");
+            opt.snappy = spec->snappy != 0;
+            opt.bti = spec->bti != 0;
+            opt.chunk_len = checked_chunk_len_arg(spec->chunk_length, CHUNK_LEN);
+            write_sstable_device(opb, rows, R, sp, d_stats, d_tomb, tomb_cap, types, opt, stream);
         }
         return GPUC_OK;
-    } catch (const unsupported_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_UNSUPPORTED;
-    } catch (const format_error& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_FORMAT;
-    } catch (const std::exception& e) {
-        set_err(error, error_len, e.what());
-        return GPUC_ERR_INTERNAL;
-    }
+    });
 }
 
 

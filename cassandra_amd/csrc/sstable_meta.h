@@ -165,14 +165,17 @@ inline ChunkWindow chunk_window(const HCompressionInfo& ci, uint64_t comp_file_s
     return w;
 }
 
-struct HStatistics {
-    // HEADER component
+// the marshal type strings of a table, as the Statistics.db HEADER lists them
+struct TableTypes {
+    std::string key_type;
+    std::vector<std::string> clustering_types;  // empty = no clustering columns
+    std::vector<std::pair<bytes, std::string>> static_cols, regular_cols;  // (name, type)
+};
+struct HStatistics : TableTypes {
+    // HEADER component (with the TableTypes base)
     int64_t hdr_min_ts = TIMESTAMP_EPOCH;
     int64_t hdr_min_ldt = DELETION_TIME_EPOCH;
     int32_t hdr_min_ttl = 0;
-    std::string key_type;
-    std::vector<std::string> clustering_types;
-    std::vector<std::pair<bytes, std::string>> static_cols, regular_cols;
     // STATS mins (for SerializationHeader.make of the output)
     int64_t min_timestamp = 0, max_timestamp = 0;
     int64_t min_ldt = NO_DELETION_TIME, max_ldt = 0;
@@ -261,15 +264,24 @@ inline void parse_index_positions(const bytes& ib, uint64_t data_len,
 // ---------------------------------------------------------------------------
 // schema: marshal type strings -> the widths the parse kernels walk with
 // ---------------------------------------------------------------------------
-// marshal type string -> clustering component width (-1 variable)
-inline int32_t ck_type_width(const std::string& t) {
+// marshal type string -> serialized value width, -1 variable. Permissive: a
+// type it does not know is variable width; callers that must refuse unknown
+// types check simple_value_type first.
+inline int32_t type_width(const std::string& t) {
     if (t == "org.apache.cassandra.db.marshal.LongType") return 8;
     if (t == "org.apache.cassandra.db.marshal.Int32Type") return 4;
-    if (t == "org.apache.cassandra.db.marshal.UTF8Type" ||
-        t == "org.apache.cassandra.db.marshal.AsciiType" ||
-        t == "org.apache.cassandra.db.marshal.BytesType")
-        return -1;
-    throw std::runtime_error("unsupported clustering type " + t);
+    return -1;
+}
+// the simple value types the engine walks
+inline bool simple_value_type(const std::string& t) {
+    return type_width(t) > 0 || t == "org.apache.cassandra.db.marshal.UTF8Type" ||
+           t == "org.apache.cassandra.db.marshal.AsciiType" ||
+           t == "org.apache.cassandra.db.marshal.BytesType";
+}
+// clustering component width; refuses every other type
+inline int32_t ck_type_width(const std::string& t) {
+    if (!simple_value_type(t)) throw std::runtime_error("unsupported clustering type " + t);
+    return type_width(t);
 }
 
 struct HostSchema {
@@ -295,12 +307,7 @@ inline HostSchema resolve_schema(const HStatistics& st) {
         if (hs.n_cpx && ct != map_bb)
             throw std::runtime_error(
                 "complex columns must follow every simple regular column");
-        if (ct == "org.apache.cassandra.db.marshal.LongType") hs.col_fixed.push_back(8);
-        else if (ct == "org.apache.cassandra.db.marshal.Int32Type") hs.col_fixed.push_back(4);
-        else if (ct == "org.apache.cassandra.db.marshal.BytesType" ||
-                 ct == "org.apache.cassandra.db.marshal.UTF8Type" ||
-                 ct == "org.apache.cassandra.db.marshal.AsciiType")
-            hs.col_fixed.push_back(-1);
+        if (simple_value_type(ct)) hs.col_fixed.push_back(type_width(ct));
         else if (ct == "org.apache.cassandra.db.marshal.CounterColumnType") {
             hs.col_fixed.push_back(-1);
             hs.counters = true;
@@ -327,14 +334,9 @@ inline HostSchema resolve_schema(const HStatistics& st) {
     }
     for (auto& t : st.clustering_types) hs.ck_widths.push_back(ck_type_width(t));
     for (auto& sc : st.static_cols) {
-        const std::string& ct2 = sc.second;
-        if (ct2 == "org.apache.cassandra.db.marshal.LongType") hs.static_fixed.push_back(8);
-        else if (ct2 == "org.apache.cassandra.db.marshal.Int32Type") hs.static_fixed.push_back(4);
-        else if (ct2 == "org.apache.cassandra.db.marshal.BytesType" ||
-                 ct2 == "org.apache.cassandra.db.marshal.UTF8Type" ||
-                 ct2 == "org.apache.cassandra.db.marshal.AsciiType")
-            hs.static_fixed.push_back(-1);
-        else throw std::runtime_error("unsupported static column type " + ct2);
+        if (!simple_value_type(sc.second))
+            throw std::runtime_error("unsupported static column type " + sc.second);
+        hs.static_fixed.push_back(type_width(sc.second));
     }
     if (hs.static_fixed.size() > 63)
         throw std::runtime_error("1..63 static columns supported");

@@ -98,6 +98,34 @@ static void check_reader() {
     r.skip(0);
 }
 
+// the one type -> width table: permissive for values (an unknown type is
+// variable width), refusing for clustering columns
+static void check_type_widths() {
+    const std::string m = "org.apache.cassandra.db.marshal.";
+    const struct { const char* type; int32_t width; } known[] = {
+        {"LongType", 8}, {"Int32Type", 4}, {"BytesType", -1}, {"UTF8Type", -1}, {"AsciiType", -1}};
+    for (auto& k : known) {
+        CHECK(type_width(m + k.type) == k.width, "type_width(%s)", k.type);
+        CHECK(simple_value_type(m + k.type), "simple_value_type(%s)", k.type);
+        CHECK(ck_type_width(m + k.type) == k.width, "ck_type_width(%s)", k.type);
+    }
+    const std::string unknown = m + "TimeUUIDType";
+    CHECK(type_width(unknown) == -1 && !simple_value_type(unknown), "unknown type");
+    CHECK(thrown([&] { ck_type_width(unknown); }) == 'r', "ck_type_width accepts an unknown type");
+    // resolve_schema keeps its own whitelist in front of the table
+    HStatistics st;
+    st.regular_cols = {{bytes{'v'}, unknown}};
+    CHECK(thrown([&] { resolve_schema(st); }) == 'r', "unknown regular column type accepted");
+    st.regular_cols = {{bytes{'v'}, m + "Int32Type"}};
+    st.static_cols = {{bytes{'s'}, unknown}};
+    CHECK(thrown([&] { resolve_schema(st); }) == 'r', "unknown static column type accepted");
+    st.static_cols = {{bytes{'s'}, m + "LongType"}};
+    st.clustering_types = {m + "UTF8Type", m + "Int32Type"};
+    HostSchema hs = resolve_schema(st);
+    CHECK(hs.col_fixed == std::vector<int32_t>{4} && hs.static_fixed == std::vector<int32_t>{8} &&
+          hs.ck_widths == (std::vector<int32_t>{-1, 4}), "resolved widths");
+}
+
 struct Input {
     std::string base;
     bytes ci_b, st_b, ix_b;
@@ -348,6 +376,7 @@ static void check_truncations(const Input& in) {
 int main(int argc, char** argv) {
     int n_damaged = 0, n_inputs = 0;
     check_reader();
+    check_type_widths();
     for (int a = 1; a < argc; a++) {
         std::string arg = argv[a];
         if (arg.compare(0, 7, "golden=") == 0) {

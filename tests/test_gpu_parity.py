@@ -312,6 +312,32 @@ def test_garbage_collect_parity_wide(ca, oracle_bin, tmp_path):
     _assert_dirs_equal(f"{d}/oa-90-big", f"{d}/oa-91-big")
 
 
+def test_reconcile_arity_buckets(ca, oracle_bin, tmp_path):
+    """k_reconcile_rows is instantiated for up to 8, 16 and 64 versions of a
+    partition and picked by source count: 9 and 17 data inputs reach the two
+    larger instantiations, 9 tombstone sources reach <16> in the
+    garbage-collect source pass."""
+    d = str(tmp_path)
+    gen = dict(rows=40, vlen=60, overlap=50, tomb=10)
+    for n in (9, 17):
+        dn = f"{d}/n{n}"
+        os.makedirs(dn)
+        _oracle_gen(dn, seed=180 + n, n=n, **gen)
+        ins = [f"{dn}/oa-{g}-big" for g in range(1, n + 1)]
+        _oracle_compact(f"{dn}/oa-90-big", ins)
+        ca.compact(ins, f"{dn}/oa-91-big")
+        _assert_dirs_equal(f"{dn}/oa-90-big", f"{dn}/oa-91-big")
+    # one key universe: the first sstable is the data, the other nine shadow it
+    dg = f"{d}/gc"
+    os.makedirs(dg)
+    _oracle_gen(dg, seed=189, n=10, **gen)
+    ins = [f"{dg}/oa-1-big"]
+    srcs = [f"{dg}/oa-{g}-big" for g in range(2, 11)]
+    _oracle_compact(f"{dg}/oa-90-big", ins, tombsrc=",".join(srcs))
+    ca.compact(ins, f"{dg}/oa-91-big", tombstone_sources=srcs)
+    _assert_dirs_equal(f"{dg}/oa-90-big", f"{dg}/oa-91-big")
+
+
 def test_flush_parity(ca, oracle_bin, tmp_path):
     """gpuc_flush (memtable-flush analog): unsorted unique-key host rows ->
     GPU token sort + writer == oracle flush of the same rows, byte for byte."""
