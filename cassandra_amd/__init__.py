@@ -49,6 +49,7 @@ class GpucJob(ctypes.Structure):
         ("n_output_shards", ctypes.c_int32),
         ("cancel_flag", ctypes.POINTER(ctypes.c_int32)),
         ("output_chunk_length", ctypes.c_uint32),
+        ("max_output_bytes", ctypes.c_uint64),
     ]
 
 
@@ -77,6 +78,7 @@ class GpucResult(ctypes.Structure):
         ("dominant_kernel_ms", ctypes.c_double),
         ("dominant_kernel_launches", ctypes.c_uint64),
         ("error", ctypes.c_char * 256),
+        ("n_outputs", ctypes.c_uint32),
     ]
 
 
@@ -175,6 +177,13 @@ def load_library(path=None):
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
             ctypes.c_char_p, ctypes.c_size_t]
         lib.gpuc_compress_buffer.restype = ctypes.c_int
+    if hasattr(lib, "gpuc_plan_size_cuts"):  # absent in frozen A/B probe builds
+        lib.gpuc_plan_size_cuts.argtypes = [
+            ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64,
+            ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+            ctypes.c_char_p, ctypes.c_size_t]
+        lib.gpuc_plan_size_cuts.restype = ctypes.c_int
     lib.gpuc_version.restype = ctypes.c_char_p
     lib.gpuc_device_count.restype = ctypes.c_int
     _lib = lib
@@ -610,6 +619,28 @@ def compress_buffer(data, chunk_length=0, snappy=False, device=0):
     return out.raw[:out_len.value], list(offs[:n.value])
 
 
+def plan_size_cuts(data, part_ends, chunk_length, snappy, max_output_bytes, device=0):
+    """Where the size-split writer (compact(max_output_bytes=...)) cuts a
+    stream of partitions, computed by the writer's own kernels (diagnostic).
+    part_ends[i] is the exclusive end offset of partition i in `data`
+    (non-decreasing; equal neighbours are dropped partitions). Returns the
+    indices of the last partition of every output but the final one."""
+    lib = load_library()
+    data = bytes(data)
+    n = len(part_ends)
+    ends = (ctypes.c_uint64 * max(n, 1))(*part_ends)
+    cuts = (ctypes.c_uint64 * max(n, 1))()
+    n_cuts = ctypes.c_uint64()
+    err = ctypes.create_string_buffer(256)
+    rc = lib.gpuc_plan_size_cuts(data, len(data), ends, n, chunk_length, 1 if snappy else 0,
+                                 max_output_bytes, device, cuts, max(n, 1),
+                                 ctypes.byref(n_cuts), err, 256)
+    if rc != 0:
+        raise GpuCompactError(
+            f"gpuc_plan_size_cuts rc={rc}: {err.value.decode(errors='replace')}")
+    return list(cuts[:n_cuts.value])
+
+
 def version():
     return load_library().gpuc_version().decode()
 
@@ -635,6 +666,7 @@ def compact(
     keep_ranges=None,
     invert_ranges=False,
     output_chunk_length=0,
+    max_output_bytes=0,
 ):
     """One compaction task (mirrors CompactionTask.runMayThrow's hot loop).
 
@@ -644,6 +676,10 @@ def compact(
     token_range: (lo, hi) inclusive token shard restriction or None.
     output_chunk_length: chunk length of the output in bytes (power of two,
       1024..65536); 0 == the chunk length of input_bases[0].
+    max_output_bytes: above 0, split the output as a Leveled compaction's
+      MaxSSTableSizeWriter does (a new sstable once the estimated on-disk
+      size exceeds this); outputs take the generation of output_base, +1,
+      +2, ...; the result's "n_outputs" says how many were written.
     """
     lib = load_library()
     job = GpucJob()
@@ -702,6 +738,7 @@ def compact(
         job.n_tomb_sources = len(tombstone_sources)
     job.cell_level_gc = 1 if cell_level_gc else 0
     job.output_chunk_length = output_chunk_length
+    job.max_output_bytes = max_output_bytes
     res = GpucResult()
     rc = lib.gpuc_compact(ctypes.byref(job), ctypes.byref(res))
     if rc != 0:
@@ -714,6 +751,7 @@ def compact(
         "partitions_out": res.partitions_out,
         "rows_in": res.rows_in,
         "rows_out": res.rows_out,
+        "n_outputs": res.n_outputs,
         "merged_counts": list(res.merged_counts),
         "ms": {
             "read_io": res.ms_read_io,
@@ -734,7 +772,7 @@ def compact(
 
 
 def validate(input_bases, out_path, now_sec=1800000000, gc_before=INT64_MIN,
-             overlaps=None, device=0):
+             overlaps=None, device=0, max_output_bytes=0):
     """VALIDATION compaction (CompactionManager.doValidationCompaction +
     Validator.rowHash): merge+purge, then per-partition repair digests
     written to out_path as (token i64 BE + 32-byte hash) records."""
@@ -754,6 +792,7 @@ def validate(input_bases, out_path, now_sec=1800000000, gc_before=INT64_MIN,
         job.n_overlaps = len(overlaps)
     job.device = device
     job.n_output_shards = 1
+    job.max_output_bytes = max_output_bytes  # rejected like sharding when above 0
     n = ctypes.c_uint64(0)
     err = ctypes.create_string_buffer(256)
     rc = lib.gpuc_validate(ctypes.byref(job), out_path.encode(), ctypes.byref(n), err, 256)

@@ -25,6 +25,7 @@
 #include <string>
 #include <thread>
 #include <future>
+#include <functional>
 #include <atomic>
 #include <fcntl.h>
 #include <unistd.h>
@@ -424,6 +425,7 @@ struct WriteDeviceOut {
     uint64_t compressed_len = 0;   // final Data.db size
     uint64_t partitions = 0, rows = 0, cells = 0;
     double ms_sizes = 0, ms_serialize = 0, ms_compress = 0, ms_d2h = 0, ms_io = 0;
+    uint32_t n_outputs = 1;  // sstables written (more than one only when size-split)
 };
 
 // The one place chunk-compress kernels are launched (sstable writer and
@@ -786,6 +788,227 @@ static void fill_meta_from_stats(OutMeta& m, const OutStats& hst, const HeaderSt
     memcpy(m.cells_hist, hst.cells_hist, sizeof(m.cells_hist));
 }
 
+// One output's device image, ready to leave the device: what the drain and
+// the component tail consume. The buffers stay the caller's.
+struct OutputImage {
+    uint64_t g0 = 0, g1 = 0;  // its groups [g0, g1)
+    uint64_t total_unc = 0, total_idx = 0;
+    uint32_t n_chunks = 0;
+    const DevBuf *slots = nullptr, *csize = nullptr, *ccrc = nullptr;  // compressed chunks
+    const DevBuf *out_index = nullptr, *bloom = nullptr;
+    uint8_t* h_index = nullptr;  // pinned, total_idx bytes
+    uint64_t words = 0;          // bloom words
+    HBloomSpec bs{};
+    OutStats hst{};
+    const std::vector<Event>* ev_c = nullptr;  // per slab: its chunks are compressed
+    bool index_late = false;  // Index.db image is fetched after the drain (gated on ev2)
+};
+
+// stages 3 and 4 of the writer: slab drain of the compressed chunks into
+// Data.db on `cstream`, then the component tail. Returns with both streams
+// idle and every component of opt.base written.
+static void drain_and_finish(const OutputImage& im, const OutPartsBuf& opb, const SerParams2& sp,
+                             const DevBuf& d_tomb, uint32_t tomb_cap, const TableTypes& types,
+                             const OutputOptions& opt, hipStream_t stream, hipStream_t cstream,
+                             hipEvent_t ev2, hipEvent_t ev4, WriteDeviceOut& w) {
+    const std::string& out_base = opt.base;
+    const bool snappy_out = opt.snappy, bti_out = opt.bti;
+    const int wslot = opt.wslot;
+    const uint32_t OCL = opt.chunk_len;
+    const uint32_t SLOT_STRIDE = snappy_out ? snp_slot_stride(OCL) : lz4_slot_stride(OCL);
+    const uint32_t SLAB = (512u << 20) / OCL;
+    const uint32_t n_chunks = im.n_chunks;
+    const uint32_t n_slabs = n_chunks ? (n_chunks + SLAB - 1) / SLAB : 0;
+    const uint64_t total_unc = im.total_unc, total_idx = im.total_idx, words = im.words;
+    uint8_t* const h_index = im.h_index;
+    const OutStats& hst = im.hst;
+    const HBloomSpec& bs = im.bs;
+    // ==== stage 3: slab drain ====
+    std::string data_path = out_base + "-Data.db";
+    write_file(data_path, nullptr, 0);  // create/truncate so writers can pwrite into it
+    const uint64_t worst_slab = (uint64_t)SLAB * ((uint64_t)SLOT_STRIDE + 4);
+    const int NSLOTS = 4;
+    uint8_t* h_slab0 = (uint8_t*)g_pin_out[wslot][0].get(worst_slab * NSLOTS);
+    if (!h_slab0) throw std::runtime_error("pinned out alloc failed");
+    DevBuf d_gat[2], d_foff[2];
+    if (n_slabs) {
+        d_gat[0].alloc(worst_slab); d_gat[1].alloc(worst_slab);
+        d_foff[0].alloc((uint64_t)SLAB * 8); d_foff[1].alloc((uint64_t)SLAB * 8);
+    }
+    std::vector<uint32_t> cs(n_chunks);
+    std::vector<uint64_t> foff_h[2];
+    foff_h[0].resize(SLAB); foff_h[1].resize(SLAB);
+    std::future<void> wfut[NSLOTS];
+    double t_drain0 = 0, t_drain1 = 0;
+    {
+        struct timespec tsd; clock_gettime(CLOCK_MONOTONIC, &tsd);
+        t_drain0 = tsd.tv_sec * 1e3 + tsd.tv_nsec / 1e6;
+    }
+    uint64_t file_off = 0;
+    double tw_comp = 0, tw_d2h = 0, tw_wfut = 0;  // drain wait breakdown (GPUC_TRACE)
+    auto wallm = []() {
+        struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
+        return t.tv_sec * 1e3 + t.tv_nsec / 1e6;
+    };
+    for (uint32_t i = 0; i < n_slabs; i++) {
+        uint32_t cb = i * SLAB, m = std::min(SLAB, n_chunks - cb);
+        HIP_CHECK(hipStreamWaitEvent(cstream, (*im.ev_c)[i], 0));
+        HIP_CHECK(hipMemcpyAsync(cs.data() + cb, im.csize->as<uint32_t>() + cb, (uint64_t)m * 4,
+                                 hipMemcpyDeviceToHost, cstream));
+        double tq0 = wallm();
+        HIP_CHECK(hipStreamSynchronize(cstream));
+        tw_comp += wallm() - tq0;
+        auto& fo = foff_h[i & 1];
+        uint64_t acc = 0;
+        for (uint32_t j = 0; j < m; j++) { fo[j] = acc; acc += cs[cb + j]; }
+        uint64_t slab_bytes = acc + (uint64_t)m * 4;
+        HIP_CHECK(hipMemcpyAsync(d_foff[i & 1].p, fo.data(), (uint64_t)m * 8,
+                                 hipMemcpyHostToDevice, cstream));
+        hipLaunchKernelGGL(k_chunk_gather, dim3(m), dim3(WAVE), 0, cstream,
+                           im.slots->as<uint8_t>() + (uint64_t)cb * SLOT_STRIDE,
+                           im.csize->as<uint32_t>() + cb, im.ccrc->as<uint32_t>() + cb,
+                           d_foff[i & 1].as<uint64_t>(), d_gat[i & 1].as<uint8_t>(), m,
+                           SLOT_STRIDE);
+        int slot = (int)(i % NSLOTS);
+        double tq1 = wallm();
+        if (wfut[slot].valid()) wfut[slot].get();  // pinned buffer free again
+        tw_wfut += wallm() - tq1;
+        uint8_t* hbuf = h_slab0 + (uint64_t)slot * worst_slab;
+        HIP_CHECK(hipMemcpyAsync(hbuf, d_gat[i & 1].p, slab_bytes, hipMemcpyDeviceToHost, cstream));
+        double tq2 = wallm();
+        HIP_CHECK(hipStreamSynchronize(cstream));
+        tw_d2h += wallm() - tq2;
+        uint64_t off0 = file_off;
+        wfut[slot] = std::async(std::launch::async, [=]() {
+            pwrite_range(data_path, hbuf, slab_bytes, off0, 4);
+        });
+        file_off += slab_bytes;
+    }
+    {
+        double tq3 = wallm();
+        for (int sfin = 0; sfin < NSLOTS; sfin++)
+            if (wfut[sfin].valid()) wfut[sfin].get();
+        tw_wfut += wallm() - tq3;
+    }
+    if (g_trace)
+        fprintf(stderr, "[drain] slabs=%u wait_compress=%.0fms wait_d2h=%.0fms wait_write=%.0fms\n",
+                n_slabs, tw_comp, tw_d2h, tw_wfut);
+    {
+        struct timespec tsd; clock_gettime(CLOCK_MONOTONIC, &tsd);
+        t_drain1 = tsd.tv_sec * 1e3 + tsd.tv_nsec / 1e6;
+    }
+    w.compressed_len = file_off;
+    TR("wsd: drain done");
+    if (im.index_late) {
+        // segmented mode: the index image drains AFTER the data drain — an
+        // earlier enqueue would gate the whole in-order cstream on ev2 (the
+        // LAST serialize segment) and collapse the drain to a tail
+        HIP_CHECK(hipStreamWaitEvent(cstream, ev2, 0));
+        HIP_CHECK(hipMemcpyAsync(h_index, im.out_index->p, total_idx, hipMemcpyDeviceToHost, cstream));
+        HIP_CHECK(hipStreamSynchronize(cstream));
+    }
+    HIP_CHECK(hipEventRecord(ev4, stream));
+
+    // ==== stage 4: component tail (bytes decided in sstable_out.h) ====
+    {
+        std::vector<uint8_t> h_bloom(words * 8);
+        std::vector<uint32_t> h_crc(n_chunks);
+        TR("wsd: tail vectors");
+        HIP_CHECK(hipMemcpy(h_bloom.data(), im.bloom->p, words * 8, hipMemcpyDeviceToHost));
+        TR("wsd: bloom d2h");
+        if (n_chunks)
+            HIP_CHECK(hipMemcpy(h_crc.data(), im.ccrc->p, (uint64_t)n_chunks * 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK(hipStreamSynchronize(cstream));
+        TR("wsd: tail synced");
+        // digest fold and the Summary.db index walk are independent of the
+        // meta build: run all three concurrently (tail was serial: ~145 ms)
+        std::future<uint32_t> fut_digest =
+            std::async(std::launch::async, [&]() { return fold_digest(h_crc, cs); });
+        std::future<bytes> fut_summary;
+        if (!bti_out)
+            fut_summary = std::async(std::launch::async,
+                                     [&]() { return summary_db(h_index, total_idx); });
+
+        std::vector<uint32_t> tombs;
+        if (hst.tomb_count) {
+            uint64_t nt = std::min<uint64_t>(hst.tomb_count, tomb_cap);
+            tombs.resize(nt);
+            HIP_CHECK(hipMemcpy(tombs.data(), d_tomb.p, nt * 4, hipMemcpyDeviceToHost));
+            if (hst.tomb_count > tomb_cap)
+                throw std::runtime_error("tombstone list overflow (internal cap)");
+        }
+        OutMeta m{};
+        {
+            // per-partition key hashes for the COMPACTION HLL (device-hashed,
+            // filtered to kept partitions on host)
+            const uint64_t n_groups = im.g1 - im.g0;
+            DevBuf d_kh;
+            d_kh.alloc(n_groups * 8 + 8);
+            uint32_t blocks = (uint32_t)((n_groups + 255) / 256);
+            if (n_groups)
+                hipLaunchKernelGGL(k_key_hash2, dim3(blocks), dim3(256), 0, stream, opb.op,
+                                   im.g1, d_kh.as<uint64_t>(), im.g0);
+            std::vector<uint64_t> kh(n_groups);
+            std::vector<uint8_t> keep(n_groups);
+            if (n_groups) {
+                HIP_CHECK(hipStreamSynchronize(stream));
+                HIP_CHECK(hipMemcpy(kh.data(), d_kh.p, n_groups * 8, hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(keep.data(), opb.op.keep + im.g0, n_groups, hipMemcpyDeviceToHost));
+            }
+            m.key_hashes.reserve(n_groups);
+            for (uint64_t g2 = 0; g2 < n_groups; g2++)
+                if (keep[g2]) m.key_hashes.push_back(kh[g2]);
+        }
+        fill_meta_from_stats(m, hst, sp.hs, types);
+        for (uint32_t tv : tombs) m.tomb_hist[tv]++;
+        m.compression_ratio = total_unc ? (double)(w.compressed_len - (uint64_t)n_chunks * 4) / (double)total_unc : -1.0;
+        if (hst.partitions_out) {
+            uint64_t fg = hst.first_group, lg = hst.last_group;
+            for (int which = 0; which < 2; which++) {
+                uint64_t g = which ? lg : fg;
+                uint64_t ka;
+                uint16_t kl;
+                HIP_CHECK(hipMemcpy(&ka, opb.op.key_addr + g, 8, hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(&kl, opb.op.klen + g, 2, hipMemcpyDeviceToHost));
+                bytes kb(kl);
+                HIP_CHECK(hipMemcpy(kb.data(), (const void*)ka, kl, hipMemcpyDeviceToHost));
+                (which ? m.last_key : m.first_key) = kb;
+            }
+        }
+        TR("wsd: meta built");
+        // Digest = CRC of the whole Data.db, folded from per-chunk CRCs in
+        // the async above (CRC concatenation is associative over (crc, len))
+        uint32_t digest = fut_digest.get();
+
+        TR("wsd: digest done");
+        struct timespec ts0, ts1;
+        clock_gettime(CLOCK_MONOTONIC, &ts0);
+        if (bti_out) {
+            bti::bytes parts_img, rows_img;
+            std::vector<int32_t> ckw;
+            for (auto& t : types.clustering_types) ckw.push_back(type_width(t));
+            build_bti_from_index_image(h_index, total_idx, total_unc, ckw, &parts_img, &rows_img);
+            write_file(out_base + "-Partitions.db", parts_img);
+            write_file(out_base + "-Rows.db", rows_img);
+        } else {
+            write_file_parallel(out_base + "-Index.db", h_index, total_idx, 4);
+        }
+        write_file(out_base + "-Filter.db", filter_db(bs.k, h_bloom));
+        write_file(out_base + "-CompressionInfo.db",
+                   compression_info_db(snappy_out, OCL, total_unc, cs));
+        write_file(out_base + "-Digest.crc32", digest_text(digest));
+        write_file(out_base + "-Statistics.db", serialize_statistics_out(m));
+        if (!bti_out) write_file(out_base + "-Summary.db", fut_summary.get());
+        write_file(out_base + "-TOC.txt", toc_text(bti_out));
+        clock_gettime(CLOCK_MONOTONIC, &ts1);
+        TR("wsd: components written");
+        // residual (non-overlapped) component writes + the Data.db drain tail
+        w.ms_io = (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) / 1e6;
+        w.ms_d2h = t_drain1 - t_drain0;  // slab drain wall (overlaps compress)
+    }
+}
+
 static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfColsBuf& rows,
                                            uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
                                            DevBuf& d_tomb, uint32_t tomb_cap,
@@ -965,189 +1188,24 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     HIP_CHECK(hipEventRecord(ev3, stream));  // ev2..ev3: compress (+interleaved serialize) GPU time
     TR("wsd: compress issued");
 
-    // ==== stage 3: slab drain ====
-    std::string data_path = out_base + "-Data.db";
-    write_file(data_path, nullptr, 0);  // create/truncate so writers can pwrite into it
-    const uint64_t worst_slab = (uint64_t)SLAB * ((uint64_t)SLOT_STRIDE + 4);
-    const int NSLOTS = 4;
-    uint8_t* h_slab0 = (uint8_t*)g_pin_out[wslot][0].get(worst_slab * NSLOTS);
-    if (!h_slab0) throw std::runtime_error("pinned out alloc failed");
-    DevBuf d_gat[2], d_foff[2];
-    if (n_slabs) {
-        d_gat[0].alloc(worst_slab); d_gat[1].alloc(worst_slab);
-        d_foff[0].alloc((uint64_t)SLAB * 8); d_foff[1].alloc((uint64_t)SLAB * 8);
-    }
-    std::vector<uint32_t> cs(n_chunks);
-    std::vector<uint64_t> foff_h[2];
-    foff_h[0].resize(SLAB); foff_h[1].resize(SLAB);
-    std::future<void> wfut[NSLOTS];
-    double t_drain0 = 0, t_drain1 = 0;
-    {
-        struct timespec tsd; clock_gettime(CLOCK_MONOTONIC, &tsd);
-        t_drain0 = tsd.tv_sec * 1e3 + tsd.tv_nsec / 1e6;
-    }
-    uint64_t file_off = 0;
-    double tw_comp = 0, tw_d2h = 0, tw_wfut = 0;  // drain wait breakdown (GPUC_TRACE)
-    auto wallm = []() {
-        struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t);
-        return t.tv_sec * 1e3 + t.tv_nsec / 1e6;
-    };
-    for (uint32_t i = 0; i < n_slabs; i++) {
-        uint32_t cb = i * SLAB, m = std::min(SLAB, n_chunks - cb);
-        HIP_CHECK(hipStreamWaitEvent(cstream, ev_c[i], 0));
-        HIP_CHECK(hipMemcpyAsync(cs.data() + cb, d_csize.as<uint32_t>() + cb, (uint64_t)m * 4,
-                                 hipMemcpyDeviceToHost, cstream));
-        double tq0 = wallm();
-        HIP_CHECK(hipStreamSynchronize(cstream));
-        tw_comp += wallm() - tq0;
-        auto& fo = foff_h[i & 1];
-        uint64_t acc = 0;
-        for (uint32_t j = 0; j < m; j++) { fo[j] = acc; acc += cs[cb + j]; }
-        uint64_t slab_bytes = acc + (uint64_t)m * 4;
-        HIP_CHECK(hipMemcpyAsync(d_foff[i & 1].p, fo.data(), (uint64_t)m * 8,
-                                 hipMemcpyHostToDevice, cstream));
-        hipLaunchKernelGGL(k_chunk_gather, dim3(m), dim3(WAVE), 0, cstream,
-                           d_slots.as<uint8_t>() + (uint64_t)cb * SLOT_STRIDE,
-                           d_csize.as<uint32_t>() + cb, d_ccrc.as<uint32_t>() + cb,
-                           d_foff[i & 1].as<uint64_t>(), d_gat[i & 1].as<uint8_t>(), m,
-                           SLOT_STRIDE);
-        int slot = (int)(i % NSLOTS);
-        double tq1 = wallm();
-        if (wfut[slot].valid()) wfut[slot].get();  // pinned buffer free again
-        tw_wfut += wallm() - tq1;
-        uint8_t* hbuf = h_slab0 + (uint64_t)slot * worst_slab;
-        HIP_CHECK(hipMemcpyAsync(hbuf, d_gat[i & 1].p, slab_bytes, hipMemcpyDeviceToHost, cstream));
-        double tq2 = wallm();
-        HIP_CHECK(hipStreamSynchronize(cstream));
-        tw_d2h += wallm() - tq2;
-        uint64_t off0 = file_off;
-        wfut[slot] = std::async(std::launch::async, [=]() {
-            pwrite_range(data_path, hbuf, slab_bytes, off0, 4);
-        });
-        file_off += slab_bytes;
-    }
-    {
-        double tq3 = wallm();
-        for (int sfin = 0; sfin < NSLOTS; sfin++)
-            if (wfut[sfin].valid()) wfut[sfin].get();
-        tw_wfut += wallm() - tq3;
-    }
-    if (g_trace)
-        fprintf(stderr, "[drain] slabs=%u wait_compress=%.0fms wait_d2h=%.0fms wait_write=%.0fms\n",
-                n_slabs, tw_comp, tw_d2h, tw_wfut);
-    {
-        struct timespec tsd; clock_gettime(CLOCK_MONOTONIC, &tsd);
-        t_drain1 = tsd.tv_sec * 1e3 + tsd.tv_nsec / 1e6;
-    }
-    w.compressed_len = file_off;
-    TR("wsd: drain done");
-    if (NSEG > 1) {
-        // segmented mode: the index image drains AFTER the data drain — an
-        // earlier enqueue would gate the whole in-order cstream on ev2 (the
-        // LAST serialize segment) and collapse the drain to a tail
-        HIP_CHECK(hipStreamWaitEvent(cstream, ev2, 0));
-        HIP_CHECK(hipMemcpyAsync(h_index, d_out_index.p, total_idx, hipMemcpyDeviceToHost, cstream));
-        HIP_CHECK(hipStreamSynchronize(cstream));
-    }
-    HIP_CHECK(hipEventRecord(ev4, stream));
-
-    // ==== stage 4: component tail (bytes decided in sstable_out.h) ====
-    {
-        std::vector<uint8_t> h_bloom(words * 8);
-        std::vector<uint32_t> h_crc(n_chunks);
-        TR("wsd: tail vectors");
-        HIP_CHECK(hipMemcpy(h_bloom.data(), d_bloom.p, words * 8, hipMemcpyDeviceToHost));
-        TR("wsd: bloom d2h");
-        if (n_chunks)
-            HIP_CHECK(hipMemcpy(h_crc.data(), d_ccrc.p, (uint64_t)n_chunks * 4, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipStreamSynchronize(cstream));
-        TR("wsd: tail synced");
-        // digest fold and the Summary.db index walk are independent of the
-        // meta build: run all three concurrently (tail was serial: ~145 ms)
-        std::future<uint32_t> fut_digest =
-            std::async(std::launch::async, [&]() { return fold_digest(h_crc, cs); });
-        std::future<bytes> fut_summary;
-        if (!bti_out)
-            fut_summary = std::async(std::launch::async,
-                                     [&]() { return summary_db(h_index, total_idx); });
-
-        std::vector<uint32_t> tombs;
-        if (hst.tomb_count) {
-            uint64_t nt = std::min<uint64_t>(hst.tomb_count, tomb_cap);
-            tombs.resize(nt);
-            HIP_CHECK(hipMemcpy(tombs.data(), d_tomb.p, nt * 4, hipMemcpyDeviceToHost));
-            if (hst.tomb_count > tomb_cap)
-                throw std::runtime_error("tombstone list overflow (internal cap)");
-        }
-        OutMeta m{};
-        {
-            // per-partition key hashes for the COMPACTION HLL (device-hashed,
-            // filtered to kept partitions on host)
-            DevBuf d_kh;
-            d_kh.alloc(n_groups * 8 + 8);
-            uint32_t blocks = (uint32_t)((n_groups + 255) / 256);
-            if (n_groups)
-                hipLaunchKernelGGL(k_key_hash2, dim3(blocks), dim3(256), 0, stream, opb.op,
-                                   n_groups, d_kh.as<uint64_t>());
-            std::vector<uint64_t> kh(n_groups);
-            std::vector<uint8_t> keep(n_groups);
-            if (n_groups) {
-                HIP_CHECK(hipStreamSynchronize(stream));
-                HIP_CHECK(hipMemcpy(kh.data(), d_kh.p, n_groups * 8, hipMemcpyDeviceToHost));
-                HIP_CHECK(hipMemcpy(keep.data(), opb.op.keep, n_groups, hipMemcpyDeviceToHost));
-            }
-            m.key_hashes.reserve(n_groups);
-            for (uint64_t g2 = 0; g2 < n_groups; g2++)
-                if (keep[g2]) m.key_hashes.push_back(kh[g2]);
-        }
-        fill_meta_from_stats(m, hst, sp.hs, types);
-        for (uint32_t tv : tombs) m.tomb_hist[tv]++;
-        m.compression_ratio = total_unc ? (double)(w.compressed_len - (uint64_t)n_chunks * 4) / (double)total_unc : -1.0;
-        if (w.partitions) {
-            uint64_t fg = hst.first_group, lg = hst.last_group;
-            for (int which = 0; which < 2; which++) {
-                uint64_t g = which ? lg : fg;
-                uint64_t ka;
-                uint16_t kl;
-                HIP_CHECK(hipMemcpy(&ka, opb.op.key_addr + g, 8, hipMemcpyDeviceToHost));
-                HIP_CHECK(hipMemcpy(&kl, opb.op.klen + g, 2, hipMemcpyDeviceToHost));
-                bytes kb(kl);
-                HIP_CHECK(hipMemcpy(kb.data(), (const void*)ka, kl, hipMemcpyDeviceToHost));
-                (which ? m.last_key : m.first_key) = kb;
-            }
-        }
-        TR("wsd: meta built");
-        // Digest = CRC of the whole Data.db, folded from per-chunk CRCs in
-        // the async above (CRC concatenation is associative over (crc, len))
-        uint32_t digest = fut_digest.get();
-
-        TR("wsd: digest done");
-        struct timespec ts0, ts1;
-        clock_gettime(CLOCK_MONOTONIC, &ts0);
-        if (bti_out) {
-            bti::bytes parts_img, rows_img;
-            std::vector<int32_t> ckw;
-            for (auto& t : types.clustering_types) ckw.push_back(type_width(t));
-            build_bti_from_index_image(h_index, total_idx, total_unc, ckw, &parts_img, &rows_img);
-            write_file(out_base + "-Partitions.db", parts_img);
-            write_file(out_base + "-Rows.db", rows_img);
-        } else {
-            write_file_parallel(out_base + "-Index.db", h_index, total_idx, 4);
-        }
-        write_file(out_base + "-Filter.db", filter_db(bs.k, h_bloom));
-        write_file(out_base + "-CompressionInfo.db",
-                   compression_info_db(snappy_out, OCL, total_unc, cs));
-        write_file(out_base + "-Digest.crc32", digest_text(digest));
-        write_file(out_base + "-Statistics.db", serialize_statistics_out(m));
-        if (!bti_out) write_file(out_base + "-Summary.db", fut_summary.get());
-        write_file(out_base + "-TOC.txt", toc_text(bti_out));
-        clock_gettime(CLOCK_MONOTONIC, &ts1);
-        TR("wsd: components written");
-        // residual (non-overlapped) component writes + the Data.db drain tail
-        w.ms_io = (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) / 1e6;
-        w.ms_d2h = t_drain1 - t_drain0;  // slab drain wall (overlaps compress)
-    }
+    OutputImage im;
+    im.g0 = 0;
+    im.g1 = n_groups;
+    im.total_unc = total_unc;
+    im.total_idx = total_idx;
+    im.n_chunks = n_chunks;
+    im.slots = &d_slots;
+    im.csize = &d_csize;
+    im.ccrc = &d_ccrc;
+    im.out_index = &d_out_index;
+    im.bloom = &d_bloom;
+    im.h_index = h_index;
+    im.words = words;
+    im.bs = bs;
+    im.hst = hst;
+    im.ev_c = &ev_c;
+    im.index_late = NSEG > 1;
+    drain_and_finish(im, opb, sp, d_tomb, tomb_cap, types, opt, stream, cstream, ev2, ev4, w);
     w.uncompressed_len = total_unc;
     float t01, t12, t23;
     HIP_CHECK(hipEventElapsedTime(&t01, ev0, ev1));
@@ -1157,6 +1215,341 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     w.ms_serialize = t12;
     w.ms_compress = t23;
     return w;
+}
+
+// ---------------------------------------------------------------------------
+// size-capped outputs (gpuc_job.max_output_bytes; MaxSSTableSizeWriter).
+// The rule is stated once, next to k_size_cut. The host only chooses how far
+// ahead of the unknown cut to serialize and compress (the speculative
+// window) and reads one SizeCutResult per window.
+// ---------------------------------------------------------------------------
+// Window = (cap / ratio) * (1 + margin) + 2 chunks of uncompressed bytes,
+// ratio = compressed/uncompressed of the inputs. The default margin is the
+// smallest of {0, 0.01, 0.02, 0.05, 0.1} that needed no second window on the
+// recorded C2-shaped run (profiles/size_split_bench_ab.json: 0.9% of the
+// compressed chunks were past a cut); everything past the cut is waste, and
+// a window that falls short is extended, never wrong.
+static double size_split_margin() {
+    if (const char* e = getenv("GPUC_SPLIT_MARGIN")) return std::max(0.0, atof(e));
+    return 0.01;
+}
+
+// compressed chunks of the output being planned; reused from one output to
+// the next (chunks restart at every output's first byte)
+struct CutPlan {
+    DevBuf slots, csize, ccrc, disk, res;
+    uint32_t cap_chunks = 0;   // allocated chunk slots
+    uint32_t chunks_done = 0;  // complete chunks compressed and scanned
+    uint64_t disk_done = 0;    // their on-disk bytes (payload + CRC)
+    uint64_t gw = 0;           // groups before gw are serialized
+    uint32_t windows = 0;      // of the current output
+    uint64_t chunks_compressed = 0;  // all outputs, for GPUC_TRACE
+    double ms_compress = 0;
+    // room for `chunks` slots; finished chunks are kept
+    void reserve(uint32_t chunks, uint32_t stride, hipStream_t stream) {
+        if (!res.p) res.alloc(sizeof(SizeCutResult));
+        if (chunks <= cap_chunks) return;
+        uint64_t want = (uint64_t)chunks + chunks / 4 + 1;
+        if (want > 0xFFFFFFFFull) throw std::runtime_error("output too large for this chunk_length");
+        DevBuf ns, nc, nr;
+        ns.alloc(want * stride + 16);
+        nc.alloc(want * 4 + 16);
+        nr.alloc(want * 4 + 16);
+        if (chunks_done) {
+            HIP_CHECK(hipMemcpyAsync(ns.p, slots.p, (uint64_t)chunks_done * stride, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(nc.p, csize.p, (uint64_t)chunks_done * 4, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(nr.p, ccrc.p, (uint64_t)chunks_done * 4, hipMemcpyDeviceToDevice, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+        }
+        std::swap(slots.p, ns.p); std::swap(slots.n, ns.n);
+        std::swap(csize.p, nc.p); std::swap(csize.n, nc.n);
+        std::swap(ccrc.p, nr.p); std::swap(ccrc.n, nr.n);
+        disk.alloc((want + 1) * 8);
+        cap_chunks = (uint32_t)want;
+    }
+};
+
+// Where does the output that starts at group g0 end? P_h holds the n+1
+// scanned offsets of the groups in the job's uncompressed stream (d_P is its
+// device copy), d_keep their keep flags, d_data the device address of byte
+// P_h[0]. `serialize(gb)` must issue on `stream` whatever makes the bytes of
+// the groups [g0, gb) valid. Returns the output's last group. Groups after
+// it may all be dropped ones (P_h[last + 1] == P_h[n]): then no partition is
+// left to start another sstable, which the callers check. On return cp holds
+// the output's complete chunks up to cp.chunks_done, compressed, and `stream`
+// is idle.
+static uint64_t plan_size_cut(CutPlan& cp, const std::vector<uint64_t>& P_h, const uint64_t* d_P,
+                              const uint8_t* d_keep, uint64_t g0, const uint8_t* d_data,
+                              double ratio, bool snappy, uint32_t L, uint64_t max_bytes,
+                              const std::function<void(uint64_t)>& serialize,
+                              hipStream_t stream) {
+    const uint64_t n = P_h.size() - 1;
+    const uint64_t B = P_h[g0], remaining = P_h[n] - B;
+    const uint32_t stride = snappy ? snp_slot_stride(L) : lz4_slot_stride(L);
+    const uint8_t* d_base = d_data + (B - P_h[0]);
+    cp.chunks_done = 0;
+    cp.disk_done = 0;
+    cp.gw = g0;
+    cp.windows = 0;
+    if (!(ratio > 0.01)) ratio = 0.01;
+    if (ratio > 1.5) ratio = 1.5;
+    double want = (double)max_bytes / ratio * (1.0 + size_split_margin()) + 2.0 * L;
+    Event eb, ee;
+    for (;;) {
+        const uint64_t U = want >= (double)remaining ? remaining : (uint64_t)want;
+        // first group boundary at or past U bytes; P_h[n] - B >= U, so it exists
+        uint64_t gb = (uint64_t)(std::lower_bound(P_h.begin() + cp.gw, P_h.end(), B + U) - P_h.begin());
+        if (gb > n) gb = n;
+        if (gb <= cp.gw) throw std::runtime_error("size split: window did not grow");
+        serialize(gb);
+        const uint64_t W = P_h[gb] - B;
+        if (W / L > 0xFFFFFFFEull) throw std::runtime_error("output too large for this chunk_length");
+        const uint32_t c1 = (uint32_t)(W / L);  // complete chunks of the window
+        cp.reserve(c1 + 1, stride, stream);     // + the short last chunk of the finished output
+        HIP_CHECK(hipEventRecord(eb, stream));
+        if (c1 > cp.chunks_done) {
+            const uint32_t c0 = cp.chunks_done;
+            launch_chunk_compress(snappy, d_base + (uint64_t)c0 * L, W - (uint64_t)c0 * L,
+                                  cp.slots.as<uint8_t>() + (uint64_t)c0 * stride,
+                                  cp.csize.as<uint32_t>() + c0, cp.ccrc.as<uint32_t>() + c0,
+                                  c1 - c0, L, stride, stream);
+            cp.chunks_compressed += c1 - c0;
+        }
+        hipLaunchKernelGGL(k_size_cut, dim3(1), dim3(SIZE_CUT_BLOCK), 0, stream, d_P + 1, d_keep,
+                           cp.gw, gb, B, cp.csize.as<uint32_t>(), cp.chunks_done, c1, cp.disk_done,
+                           L, max_bytes, cp.disk.as<uint64_t>(), cp.res.as<SizeCutResult>());
+        HIP_CHECK(hipEventRecord(ee, stream));
+        SizeCutResult r;
+        HIP_CHECK(hipMemcpyAsync(&r, cp.res.p, sizeof(r), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        float ms;
+        HIP_CHECK(hipEventElapsedTime(&ms, eb, ee));
+        cp.ms_compress += ms;
+        cp.windows++;
+        cp.chunks_done = c1;
+        cp.disk_done = r.disk;
+        cp.gw = gb;
+        if (r.cut != SIZE_CUT_NONE) {
+            if (r.cut < g0 || r.cut >= gb) throw std::runtime_error("size split: cut outside its window");
+            return r.cut;
+        }
+        if (W == remaining) return gb - 1;  // no cut before the job's last byte
+        want = std::max(want * 2.0, (double)W + 2.0 * L);
+    }
+}
+
+// "<dir>/<version>-<generation>-<format>" with the generation advanced by i
+static std::string output_base_plus(const std::string& ob, uint64_t i) {
+    if (!i) return ob;
+    size_t sl = ob.rfind('/');
+    std::string dir = sl == std::string::npos ? std::string() : ob.substr(0, sl + 1);
+    std::string name = sl == std::string::npos ? ob : ob.substr(sl + 1);
+    size_t a = name.find('-'), b2 = a == std::string::npos ? a : name.find('-', a + 1);
+    if (b2 == std::string::npos) throw unsupported_error("output_base has no generation to advance");
+    uint64_t gen0 = std::stoull(name.substr(a + 1, b2 - a - 1));
+    return dir + name.substr(0, a + 1) + std::to_string(gen0 + i) + name.substr(b2);
+}
+
+// The size-split writer: stage 1 (sizes) once for all groups, then per
+// output a speculative window (serialize + compress + k_size_cut, extended
+// until the cut is inside it), and the ordinary drain and tail over the
+// output's own groups. `ratio` is the inputs' compressed/uncompressed ratio;
+// `poll` is called between outputs (cancellation). opt.base names the first
+// output, the following ones advance its generation.
+static WriteDeviceOut write_sstables_size_split(const OutPartsBuf& opb, const UnfColsBuf& rows,
+                                                uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
+                                                DevBuf& d_tomb, uint32_t tomb_cap,
+                                                const TableTypes& types, const OutputOptions& opt,
+                                                uint64_t max_bytes, double ratio,
+                                                const std::function<void()>& poll,
+                                                hipStream_t stream) {
+    if (!chunk_len_supported(opt.chunk_len))
+        throw unsupported_error("unsupported output chunk_length " + std::to_string(opt.chunk_len) +
+                                CHUNK_LEN_WHY);
+    const uint32_t OCL = opt.chunk_len;
+    const uint32_t SLOT_STRIDE = opt.snappy ? snp_slot_stride(OCL) : lz4_slot_stride(OCL);
+    static const std::vector<int64_t> ps_off_h = est_hist_offsets(155);
+    static const std::vector<int64_t> ch_off_h = est_hist_offsets(118);
+    DevBuf d_ps_off, d_ch_off;
+    d_ps_off.alloc(ps_off_h.size() * 8);
+    d_ch_off.alloc(ch_off_h.size() * 8);
+    HIP_CHECK(hipMemcpyAsync(d_ps_off.p, ps_off_h.data(), ps_off_h.size() * 8, hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(d_ch_off.p, ch_off_h.data(), ch_off_h.size() * 8, hipMemcpyHostToDevice, stream));
+
+    // ==== stage 1, once: partition sizes are position-independent ====
+    DevBuf d_psize, d_poff, d_rel, d_isize, d_nblocks, d_infsz, d_cells;
+    d_psize.alloc((n_groups + 1) * 8);
+    d_poff.alloc((n_groups + 1) * 8);
+    d_rel.alloc((n_groups + 1) * 8);  // offsets relative to the current output's first byte
+    d_isize.alloc((n_groups + 1) * 8);
+    d_nblocks.alloc(n_groups * 4);
+    d_infsz.alloc(n_groups * 8);
+    d_cells.alloc(n_groups * 8);
+    uint64_t total_unc = 0;
+    float ms_sizes = 0;
+    if (n_groups) {
+        Event es0, es1;
+        HIP_CHECK(hipEventRecord(es0, stream));
+        hipLaunchKernelGGL(k_sizes_rows, dim3((uint32_t)((n_groups + 255) / 256)), dim3(256), 0,
+                           stream, opb.op, rows.uc, n_groups, sp, d_psize.as<uint64_t>(),
+                           d_isize.as<uint64_t>(), d_nblocks.as<uint32_t>(),
+                           d_infsz.as<uint64_t>(), (OutStats*)nullptr, d_ps_off.as<int64_t>(),
+                           (int32_t)ps_off_h.size(), d_ch_off.as<int64_t>(),
+                           (int32_t)ch_off_h.size(), d_cells.as<uint64_t>());
+        HIP_CHECK(hipEventRecord(es1, stream));
+        HIP_CHECK(hipMemsetAsync(d_psize.as<uint64_t>() + n_groups, 0, 8, stream));
+        HIP_CHECK(hipMemcpyAsync(d_poff.p, d_psize.p, (n_groups + 1) * 8, hipMemcpyDeviceToDevice, stream));
+        total_unc = exscan_u64(d_poff.as<uint64_t>(), n_groups + 1, stream);
+        HIP_CHECK(hipEventElapsedTime(&ms_sizes, es0, es1));
+    }
+    // nothing kept: the one empty sstable the unsplit writer produces
+    if (!total_unc)
+        return write_sstable_device(opb, rows, n_groups, sp, d_stats, d_tomb, tomb_cap, types, opt,
+                                    stream);
+    std::vector<uint64_t> P_h(n_groups + 1);
+    HIP_CHECK(hipMemcpy(P_h.data(), d_poff.p, (n_groups + 1) * 8, hipMemcpyDeviceToHost));
+
+    WriteDeviceOut tot;
+    tot.n_outputs = 0;
+    tot.ms_sizes = ms_sizes;
+    DevBuf d_out_data, d_out_index, d_bloom, d_stats_k;
+    d_out_data.alloc(total_unc);
+    d_stats_k.alloc(sizeof(OutStats));
+    Stream cstream;
+    Event ev2, ev4, evs0, evs1;
+    CutPlan cp;
+    uint64_t chunks_written = 0, windows_total = 0, unc_serialized = 0;
+    const HBloomSpec bs = bloom_spec_001();
+    for (uint64_t g0 = 0; g0 < n_groups && P_h[g0] < total_unc;) {
+        poll();
+        const uint64_t B = P_h[g0];
+        uint64_t idx_n = 0;  // groups covered by the window's Index.db offsets
+        bool timed = false;
+        auto add_serialize_ms = [&]() {
+            if (!timed) return;
+            float ms;
+            HIP_CHECK(hipEventElapsedTime(&ms, evs0, evs1));
+            tot.ms_serialize += ms;
+            timed = false;
+        };
+        // Index.db entry sizes depend on positions inside THIS output, so the
+        // window's sizes, offsets and image are redone from g0 when it grows;
+        // Data bytes come out the same and finished chunks are kept
+        auto serialize = [&](uint64_t gb) {
+            add_serialize_ms();  // an earlier window of this output; stream is idle
+            const uint64_t ng = gb - g0;
+            HIP_CHECK(hipEventRecord(evs0, stream));
+            hipLaunchKernelGGL(k_index_sizes_rows, dim3((uint32_t)((ng + 255) / 256)), dim3(256), 0,
+                               stream, opb.op, gb, sp, d_poff.as<uint64_t>(),
+                               d_nblocks.as<uint32_t>(), d_infsz.as<uint64_t>(),
+                               d_isize.as<uint64_t>(), g0, B, d_rel.as<uint64_t>());
+            HIP_CHECK(hipMemsetAsync(d_isize.as<uint64_t>() + gb, 0, 8, stream));
+            uint64_t idx_w = exscan_u64(d_isize.as<uint64_t>() + g0, ng + 1, stream);
+            d_out_index.alloc(idx_w);
+            const uint32_t waves_per_block = 4;
+            hipLaunchKernelGGL(k_serialize_rows, dim3((uint32_t)((ng + waves_per_block - 1) / waves_per_block)),
+                               dim3(WAVE * waves_per_block), 0, stream, opb.op, rows.uc, gb, sp,
+                               d_rel.as<uint64_t>(), d_isize.as<uint64_t>(),
+                               d_nblocks.as<uint32_t>(), d_infsz.as<uint64_t>(),
+                               d_out_data.as<uint8_t>() + B, d_out_index.as<uint8_t>(),
+                               (uint32_t*)nullptr, (uint64_t)0, 0, g0);
+            HIP_CHECK(hipEventRecord(evs1, stream));
+            timed = true;
+            idx_n = ng;
+            unc_serialized += P_h[gb] - B;
+        };
+        const uint64_t g_last = plan_size_cut(cp, P_h, d_poff.as<uint64_t>(), opb.op.keep, g0,
+                                              d_out_data.as<uint8_t>(), ratio, opt.snappy, OCL,
+                                              max_bytes, serialize, stream);
+        add_serialize_ms();
+        const uint64_t g1 = g_last + 1;
+        if (g1 - g0 > idx_n) throw std::runtime_error("size split: cut past the serialized window");
+
+        // ==== finish output over [g0, g1): chunks before the cut are final ====
+        OutputImage im;
+        im.g0 = g0;
+        im.g1 = g1;
+        im.total_unc = P_h[g1] - B;
+        im.n_chunks = (uint32_t)((im.total_unc + OCL - 1) / OCL);
+        const uint32_t full = (uint32_t)(im.total_unc / OCL);
+        if (full > cp.chunks_done || im.n_chunks > cp.cap_chunks)
+            throw std::runtime_error("size split: chunk bookkeeping");
+        if (im.n_chunks > full) {
+            // only the last, now shorter, chunk is compressed again
+            launch_chunk_compress(opt.snappy, d_out_data.as<uint8_t>() + B + (uint64_t)full * OCL,
+                                  im.total_unc - (uint64_t)full * OCL,
+                                  cp.slots.as<uint8_t>() + (uint64_t)full * SLOT_STRIDE,
+                                  cp.csize.as<uint32_t>() + full, cp.ccrc.as<uint32_t>() + full, 1,
+                                  OCL, SLOT_STRIDE, stream);
+            cp.chunks_compressed++;
+        }
+        const uint32_t SLAB = (512u << 20) / OCL;
+        std::vector<Event> ev_c((im.n_chunks + SLAB - 1) / SLAB);
+        for (auto& e : ev_c) HIP_CHECK(hipEventRecord(e, stream));
+        HIP_CHECK(hipMemcpyAsync(&im.total_idx, d_isize.as<uint64_t>() + g1, 8, hipMemcpyDeviceToHost, stream));
+        // stats, tombstone list and histograms of the output's own groups
+        init_outstats(d_stats_k, stream);
+        {
+            const uint32_t blocks = (uint32_t)((g1 - g0 + 255) / 256);
+            hipLaunchKernelGGL(k_collect_rows, dim3(blocks), dim3(256), 0, stream, opb.op, rows.uc,
+                               g1, sp.sch.n_cols, sp.sch.n_cpx, d_stats_k.as<OutStats>(),
+                               d_tomb.as<uint32_t>(), tomb_cap, g0);
+            hipLaunchKernelGGL(k_part_hists, dim3(blocks), dim3(256), 0, stream,
+                               d_psize.as<uint64_t>(), d_cells.as<uint64_t>(), g1,
+                               d_stats_k.as<OutStats>(), d_ps_off.as<int64_t>(),
+                               (int32_t)ps_off_h.size(), d_ch_off.as<int64_t>(),
+                               (int32_t)ch_off_h.size(), g0);
+        }
+        HIP_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK(hipMemcpy(&im.hst, d_stats_k.p, sizeof(OutStats), hipMemcpyDeviceToHost));
+        const uint64_t num_bits = im.hst.partitions_out * (uint64_t)bs.buckets + 20;
+        im.words = ((num_bits - 1) >> 6) + 1;
+        im.bs = bs;
+        d_bloom.alloc(im.words * 8);
+        HIP_CHECK(hipMemsetAsync(d_bloom.p, 0, im.words * 8, stream));
+        hipLaunchKernelGGL(k_bloom_rows, dim3((uint32_t)((g1 - g0 + 255) / 256)), dim3(256), 0,
+                           stream, opb.op, g1, d_bloom.as<uint32_t>(), im.words * 64, bs.k, g0);
+        HIP_CHECK(hipEventRecord(ev2, stream));
+        im.slots = &cp.slots;
+        im.csize = &cp.csize;
+        im.ccrc = &cp.ccrc;
+        im.out_index = &d_out_index;
+        im.bloom = &d_bloom;
+        im.h_index = (uint8_t*)g_pin_out[opt.wslot][1].get(im.total_idx ? im.total_idx : 1);
+        if (!im.h_index) throw std::runtime_error("pinned out alloc failed");
+        im.ev_c = &ev_c;
+        im.index_late = true;
+        OutputOptions opt_k = opt;
+        opt_k.base = output_base_plus(opt.base, tot.n_outputs);
+        WriteDeviceOut w;
+        drain_and_finish(im, opb, sp, d_tomb, tomb_cap, types, opt_k, stream, cstream, ev2, ev4, w);
+        if (g_trace)
+            fprintf(stderr, "[split] output %u groups=[%llu,%llu) unc=%llu comp=%llu windows=%u\n",
+                    tot.n_outputs, (unsigned long long)g0, (unsigned long long)g1,
+                    (unsigned long long)im.total_unc, (unsigned long long)w.compressed_len,
+                    cp.windows);
+        tot.n_outputs++;
+        tot.partitions += im.hst.partitions_out;
+        tot.rows += im.hst.rows_out;
+        tot.cells += im.hst.total_cells;
+        tot.uncompressed_len += im.total_unc;
+        tot.compressed_len += w.compressed_len;
+        tot.ms_d2h += w.ms_d2h;
+        tot.ms_io += w.ms_io;
+        chunks_written += im.n_chunks;
+        windows_total += cp.windows;
+        g0 = g1;
+    }
+    tot.ms_compress = cp.ms_compress;
+    if (g_trace)
+        fprintf(stderr,
+                "[split] outputs=%u windows=%llu chunks_compressed=%llu chunks_written=%llu "
+                "bytes_serialized=%llu bytes_written=%llu margin=%.3f ratio=%.3f\n",
+                tot.n_outputs, (unsigned long long)windows_total,
+                (unsigned long long)cp.chunks_compressed, (unsigned long long)chunks_written,
+                (unsigned long long)unc_serialized, (unsigned long long)total_unc,
+                size_split_margin(), ratio);
+    return tot;
 }
 
 }  // namespace gpuc
@@ -1743,9 +2136,23 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             }
             return;
         }
-        WriteDeviceOut w = write_sstable_device(
-            opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb, tomb_cap, stats[0],
-            OutputOptions{out_base_str, su.cinfos[0].snappy, su.bti, su.out_chunk_len, wslot}, stream);
+        const OutputOptions oopt{out_base_str, su.cinfos[0].snappy, su.bti, su.out_chunk_len, wslot};
+        WriteDeviceOut w;
+        if (job->max_output_bytes) {
+            // r of the speculative window: the inputs' own compressed/uncompressed ratio
+            uint64_t in_comp = 0, in_unc = 0;
+            for (int s = 0; s < kd; s++) {
+                in_comp += su.comp_file_sz[s];
+                in_unc += cinfos[s].data_len;
+            }
+            w = write_sstables_size_split(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
+                                          tomb_cap, stats[0], oopt, job->max_output_bytes,
+                                          in_unc ? (double)in_comp / (double)in_unc : 1.0,
+                                          [&]() { check_cancel(job); }, stream);
+        } else {
+            w = write_sstable_device(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
+                                     tomb_cap, stats[0], oopt, stream);
+        }
         TR("writer done");
         {
             OutStats hst;
@@ -1757,6 +2164,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             HIP_CHECK(hipEventElapsedTime(&tmerge, e3, e4));
             HIP_CHECK(hipEventElapsedTime(&trec, er0, er1));
             std::lock_guard<std::mutex> g(res_mu);
+            res->n_outputs += w.n_outputs;
             res->partitions_out += w.partitions;
             res->rows_out += w.rows;
             res->output_uncompressed_bytes += w.uncompressed_len;
@@ -1966,8 +2374,10 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
             set_err(res->error, sizeof(res->error), "n_inputs (+ tombstone sources) must be 1..64");
             return GPUC_ERR_UNSUPPORTED;
         }
-        // argument check first: a bad output length never reads a byte
+        // argument checks first: a bad output length or mode never reads a byte
         (void)checked_chunk_len_arg(job->output_chunk_length, CHUNK_LEN);
+        if (job->max_output_bytes && job->n_output_shards > 1)
+            throw unsupported_error("max_output_bytes + n_output_shards unsupported");
         double t0 = wall();
         int S_pre = job->n_output_shards > 1 ? job->n_output_shards : 1;
         CompactSetup su;
@@ -2962,8 +3372,10 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
 
 extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
                              char* error, size_t error_len) {
-    if (job->n_output_shards > 1 || job->n_tomb_sources > 0 || job->n_keep_ranges > 0) {
-        set_err(error, error_len, "validation: sharding/tomb-source/keep-range modes unsupported");
+    if (job->n_output_shards > 1 || job->max_output_bytes || job->n_tomb_sources > 0 ||
+        job->n_keep_ranges > 0) {
+        set_err(error, error_len,
+                "validation: sharding/size-split/tomb-source/keep-range modes unsupported");
         return GPUC_ERR_UNSUPPORTED;
     }
     gpuc_result res{};
@@ -3186,6 +3598,63 @@ extern "C" int gpuc_compress_buffer(const uint8_t* data, uint64_t len, uint32_t 
         }
         if (out_len) *out_len = total;
         if (n_chunks_out) *n_chunks_out = n_chunks;
+        return GPUC_OK;
+    } catch (const unsupported_error& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_UNSUPPORTED;
+    } catch (const std::exception& e) {
+        set_err(error, error_len, e.what());
+        return GPUC_ERR_INTERNAL;
+    }
+}
+
+// Diagnostic: the cut points of the size-split writer over a host buffer,
+// through plan_size_cut (the writer's own launches: launch_chunk_compress and
+// k_size_cut), with part_ends standing in for the serialized partitions.
+extern "C" int gpuc_plan_size_cuts(const uint8_t* data, uint64_t len, const uint64_t* part_ends,
+                                   uint64_t n_parts, uint32_t chunk_length, int32_t snappy,
+                                   uint64_t max_output_bytes, int32_t device, uint64_t* cut_after,
+                                   uint64_t cut_cap, uint64_t* n_cuts, char* error,
+                                   size_t error_len) {
+    try {
+        if (gpuc_device_count() <= 0) { set_err(error, error_len, "no HIP device"); return GPUC_ERR_NO_GPU; }
+        const uint32_t cl = checked_chunk_len_arg(chunk_length, CHUNK_LEN);
+        if (!max_output_bytes) throw unsupported_error("max_output_bytes must be above 0");
+        if ((!data && len) || (!part_ends && n_parts)) throw unsupported_error("null data");
+        std::vector<uint64_t> P_h(n_parts + 1, 0);
+        std::vector<uint8_t> keep(n_parts ? n_parts : 1, 0);
+        for (uint64_t i = 0; i < n_parts; i++) {
+            if (part_ends[i] < P_h[i] || part_ends[i] > len)
+                throw unsupported_error("part_ends must be non-decreasing and within the buffer");
+            P_h[i + 1] = part_ends[i];
+            keep[i] = part_ends[i] > P_h[i];
+        }
+        uint64_t cuts = 0;
+        const uint64_t total = P_h[n_parts];
+        if (total) {
+            HIP_CHECK(hipSetDevice(device));
+            Stream stream;
+            ensure_crc_tables(stream);
+            DevBuf d_in, d_P, d_keep;
+            d_in.alloc(total);
+            d_P.alloc((n_parts + 1) * 8);
+            d_keep.alloc(n_parts);
+            HIP_CHECK(hipMemcpyAsync(d_in.p, data, total, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_P.p, P_h.data(), (n_parts + 1) * 8, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_keep.p, keep.data(), n_parts, hipMemcpyHostToDevice, stream));
+            CutPlan cp;
+            for (uint64_t g0 = 0; g0 < n_parts && P_h[g0] < total;) {
+                uint64_t g_last = plan_size_cut(cp, P_h, d_P.as<uint64_t>(), d_keep.as<uint8_t>(), g0,
+                                                d_in.as<uint8_t>(), 1.0, snappy != 0, cl,
+                                                max_output_bytes, [](uint64_t) {}, stream);
+                if (g_last + 1 < n_parts && P_h[g_last + 1] < total) {
+                    if (cuts >= cut_cap) throw unsupported_error("cut_cap too small");
+                    cut_after[cuts++] = g_last;
+                }
+                g0 = g_last + 1;
+            }
+        }
+        if (n_cuts) *n_cuts = cuts;
         return GPUC_OK;
     } catch (const unsupported_error& e) {
         set_err(error, error_len, e.what());

@@ -522,10 +522,11 @@ __device__ inline uint64_t murmur2_64(const uint8_t* key, uint32_t length) {
     return h;
 }
 
-__global__ void k_key_hash2(OutParts op, uint64_t n, uint64_t* out) {
-    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// groups [g0, n); out is indexed from g0
+__global__ void k_key_hash2(OutParts op, uint64_t n, uint64_t* out, uint64_t g0 = 0) {
+    uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
-    out[g] = op.keep[g] ? murmur2_64((const uint8_t*)op.key_addr[g], op.klen[g]) : 0;
+    out[g - g0] = op.keep[g] ? murmur2_64((const uint8_t*)op.key_addr[g], op.klen[g]) : 0;
 }
 
 // block-reduced merged-arity histogram (fed from op.merged_k)
@@ -2466,12 +2467,23 @@ __device__ uint64_t part_walk(const OutParts& op, const UnfCols& out, uint64_t g
     return pos;
 }
 
-// SIZE pass: psize/isize (+nblocks, infos_size) + output-stats histograms
+// EstimatedHistogram bucket of v: first offset >= v
+__device__ inline int est_hist_bucket(const int64_t* off, int32_t n, uint64_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) { int mid = (lo + hi) >> 1; if ((uint64_t)off[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// SIZE pass: psize/isize (+nblocks, infos_size) + output-stats histograms.
+// With cells_out the per-partition cell counts are stored instead and the
+// histograms are left to k_part_hists (a size-split job sizes every group
+// once, but each output histograms only its own groups); st may then be null.
 __global__ void k_sizes_rows(OutParts op, UnfCols out, uint64_t n, SerParams2 sp,
                              uint64_t* psize, uint64_t* isize, uint32_t* nblocks,
                              uint64_t* infos_size, OutStats* st,
                              const int64_t* ps_hist_off, int32_t ps_hist_n,
-                             const int64_t* ch_hist_off, int32_t ch_hist_n) {
+                             const int64_t* ch_hist_off, int32_t ch_hist_n,
+                             uint64_t* cells_out = nullptr) {
     __shared__ unsigned int sh_ps[156], sh_ch[119];
     for (int i = threadIdx.x; i < 156; i += blockDim.x) sh_ps[i] = 0;
     for (int i = threadIdx.x; i < 119; i += blockDim.x) sh_ch[i] = 0;
@@ -2485,10 +2497,8 @@ __global__ void k_sizes_rows(OutParts op, UnfCols out, uint64_t n, SerParams2 sp
         isize[g] = 0;  // computed by k_index_sizes_rows once data offsets exist
         nblocks[g] = nb;
         infos_size[g] = inf;
+        if (cells_out) cells_out[g] = 0;
         if (s) {
-            int lo = 0, hi = ps_hist_n;
-            while (lo < hi) { int mid = (lo + hi) >> 1; if ((uint64_t)ps_hist_off[mid] < s) lo = mid + 1; else hi = mid; }
-            atomicAdd(&sh_ps[lo], 1u);
             uint64_t cells = 0;
             for (uint32_t j = 0; j < op.row_count[g]; j++) {
                 uint64_t ro = op.row_base[g] + j;
@@ -2497,10 +2507,35 @@ __global__ void k_sizes_rows(OutParts op, UnfCols out, uint64_t n, SerParams2 sp
                 for (uint32_t x = 0; x < sp.sch.n_cpx && (out.flags[ro] & PF_HAS_CPX); x++)
                     if (out.cpx_present[ro * sp.sch.n_cpx + x]) cells += out.cpx_count[ro * sp.sch.n_cpx + x];
             }
-            lo = 0; hi = ch_hist_n;
-            while (lo < hi) { int mid = (lo + hi) >> 1; if ((uint64_t)ch_hist_off[mid] < cells) lo = mid + 1; else hi = mid; }
-            atomicAdd(&sh_ch[lo], 1u);
+            if (cells_out) {
+                cells_out[g] = cells;
+            } else {
+                atomicAdd(&sh_ps[est_hist_bucket(ps_hist_off, ps_hist_n, s)], 1u);
+                atomicAdd(&sh_ch[est_hist_bucket(ch_hist_off, ch_hist_n, cells)], 1u);
+            }
         }
+    }
+    __syncthreads();
+    if (cells_out) return;
+    for (int i = threadIdx.x; i < 156; i += blockDim.x)
+        if (sh_ps[i]) atomicAdd(&st->part_size_hist[i], (unsigned long long)sh_ps[i]);
+    for (int i = threadIdx.x; i < 119; i += blockDim.x)
+        if (sh_ch[i]) atomicAdd(&st->cells_hist[i], (unsigned long long)sh_ch[i]);
+}
+
+// the two histograms of k_sizes_rows over the groups [g0, n) of one output,
+// from the sizes and cell counts that pass stored
+__global__ void k_part_hists(const uint64_t* psize, const uint64_t* cells, uint64_t n,
+                             OutStats* st, const int64_t* ps_hist_off, int32_t ps_hist_n,
+                             const int64_t* ch_hist_off, int32_t ch_hist_n, uint64_t g0) {
+    __shared__ unsigned int sh_ps[156], sh_ch[119];
+    for (int i = threadIdx.x; i < 156; i += blockDim.x) sh_ps[i] = 0;
+    for (int i = threadIdx.x; i < 119; i += blockDim.x) sh_ch[i] = 0;
+    __syncthreads();
+    uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n && psize[g]) {
+        atomicAdd(&sh_ps[est_hist_bucket(ps_hist_off, ps_hist_n, psize[g])], 1u);
+        atomicAdd(&sh_ch[est_hist_bucket(ch_hist_off, ch_hist_n, cells[g])], 1u);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 156; i += blockDim.x)
@@ -2510,13 +2545,18 @@ __global__ void k_sizes_rows(OutParts op, UnfCols out, uint64_t n, SerParams2 sp
 }
 
 // index entry sizes — needs the scanned Data offsets (the position vint's
-// width depends on the partition's absolute position)
+// width depends on the partition's absolute position). Groups [g0, n) of an
+// output whose first byte is data_off value data_base; rel_off, when given,
+// receives their offsets relative to that byte (what k_serialize_rows takes
+// as data_off for such an output).
 __global__ void k_index_sizes_rows(OutParts op, uint64_t n, SerParams2 sp,
                                    const uint64_t* data_off,
                                    const uint32_t* nblocks, const uint64_t* infos_size,
-                                   uint64_t* isize) {
-    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+                                   uint64_t* isize, uint64_t g0 = 0, uint64_t data_base = 0,
+                                   uint64_t* rel_off = nullptr) {
+    uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
+    if (rel_off) rel_off[g] = data_off[g] - data_base;
     if (!op.keep[g]) { isize[g] = 0; return; }
     uint32_t klen = op.klen[g];
     bool pdel_live = op.pdel_mfda[g] == INT64_MIN && op.pdel_ldt[g] == LDT_NONE_U32;
@@ -2525,7 +2565,7 @@ __global__ void k_index_sizes_rows(OutParts op, uint64_t n, SerParams2 sp,
     // part_walk's computation
     uint64_t header_len = 2 + klen + (pdel_live ? 1 : 12) +
                           (sp.sch.n_static ? static_row_bytes(op, g, sp, nullptr, 0, 0, 0) : 0);
-    uint64_t e = 2 + klen + uvint_size(data_off[g]);
+    uint64_t e = 2 + klen + uvint_size(data_off[g] - data_base);
     uint32_t nb = nblocks[g];
     if (nb > 1) {
         uint64_t S = uvint_size(header_len) + dt_ser_size(op.pdel_mfda[g], op.pdel_ldt[g]) +
@@ -2537,7 +2577,24 @@ __global__ void k_index_sizes_rows(OutParts op, uint64_t n, SerParams2 sp,
     isize[g] = e;
 }
 
-// EMIT pass: wave per partition (Data + Index + bloom)
+__device__ inline void bloom_add_key(OutParts op, uint64_t g, uint32_t* bloom_bits,
+                                     uint64_t bloom_bitlen, int32_t bloom_k) {
+    uint32_t klen = op.klen[g];
+    uint64_t h[2];
+    murmur3_128((const uint8_t*)op.key_addr[g], klen, 0, h);
+    int64_t base = (int64_t)h[1], inc = (int64_t)h[0];
+    for (int i = 0; i < bloom_k; i++) {
+        int64_t m = base % (int64_t)bloom_bitlen;
+        uint64_t idx = (uint64_t)((m ^ (m >> 63)) - (m >> 63));
+        atomicOr(&bloom_bits[idx >> 5], 1u << (idx & 31));
+        base += inc;
+    }
+}
+
+// EMIT pass: wave per partition (Data + Index + bloom), groups [g0, n);
+// data_off and idx_off are relative to out_data / out_index. A null
+// bloom_bits leaves the filter to k_bloom_rows: a size-split output knows its
+// key count, and so its filter size, only after its cut.
 __global__ void k_serialize_rows(OutParts op, UnfCols out, uint64_t n, SerParams2 sp,
                                  const uint64_t* data_off, const uint64_t* idx_off,
                                  const uint32_t* nblocks, const uint64_t* infos_size,
@@ -2549,24 +2606,119 @@ __global__ void k_serialize_rows(OutParts op, UnfCols out, uint64_t n, SerParams
     int lane = threadIdx.x & (WAVE - 1);
     part_walk<true>(op, out, g, sp, data_off[g], idx_off[g], infos_size[g], nblocks[g],
                     out_data, out_index, lane, nullptr, nullptr, nullptr);
-    if (lane == 0) {
-        uint32_t klen = op.klen[g];
-        uint64_t h[2];
-        murmur3_128((const uint8_t*)op.key_addr[g], klen, 0, h);
-        int64_t base = (int64_t)h[1], inc = (int64_t)h[0];
-        for (int i = 0; i < bloom_k; i++) {
-            int64_t m = base % (int64_t)bloom_bitlen;
-            uint64_t idx = (uint64_t)((m ^ (m >> 63)) - (m >> 63));
-            atomicOr(&bloom_bits[idx >> 5], 1u << (idx & 31));
-            base += inc;
+    if (lane == 0 && bloom_bits) bloom_add_key(op, g, bloom_bits, bloom_bitlen, bloom_k);
+}
+
+// bloom bits of the kept groups in [g0, n)
+__global__ void k_bloom_rows(OutParts op, uint64_t n, uint32_t* bloom_bits,
+                             uint64_t bloom_bitlen, int32_t bloom_k, uint64_t g0) {
+    uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n || !op.keep[g]) return;
+    bloom_add_key(op, g, bloom_bits, bloom_bitlen, bloom_k);
+}
+
+// ---------------------------------------------------------------------------
+// size-capped outputs (MaxSSTableSizeWriter). THE RULE, stated here and in
+// tests/native/size_split_ref.cpp and nowhere else:
+//
+//   Before partition p is appended, a new sstable is started iff the current
+//   sstable already holds at least one partition and its estimated on-disk
+//   bytes exceed max_output_bytes
+//   (CompactionAwareWriter.maybeSwitchWriter,
+//    MaxSSTableSizeWriter.shouldSwitchWriterInCurrentLocation).
+//   The estimate is the compressed size of the chunks already FLUSHED
+//   (CompressedSequentialWriter.getEstimatedOnDiskBytesWritten returns
+//   chunkOffset), and a chunk is flushed lazily, when the next byte arrives
+//   at a full buffer (BufferedDataOutputStreamPlus.write / doFlush), not when
+//   the buffer becomes full.
+//
+// With E the uncompressed bytes the sstable holds after its last appended
+// partition, L the chunk length and csize[c] the compressed payload length of
+// its chunk c:
+//   flushed(E) = 0 if E == 0, else (E - 1) / L   (E == k*L leaves chunk k-1 unflushed)
+//   est(E)     = sum over c < flushed(E) of (csize[c] + 4)     (+4: the chunk CRC)
+//   cut after partition i  <=>  est(E_i) > max_output_bytes    (strictly)
+// ---------------------------------------------------------------------------
+GPUC_HD inline uint64_t size_cut_flushed_chunks(uint64_t E, uint32_t L) {
+    return E ? (E - 1) / L : 0;
+}
+
+struct SizeCutResult {
+    unsigned long long cut;   // first kept group whose estimate exceeds the cap, or SIZE_CUT_NONE
+    unsigned long long disk;  // on-disk bytes of the chunks scanned so far
+};
+#define SIZE_CUT_NONE 0xFFFFFFFFFFFFFFFFULL
+#define SIZE_CUT_BLOCK 1024
+
+// One window of one output, one block. ends[g] is the exclusive end offset of
+// group g in the job's stream and `base` the offset of the output's first
+// byte; the groups [g0, g1) are new in this window, and so are the complete
+// chunks [c0, c1) of the output, whose payload sizes are csize[c0..c1);
+// disk0 is the on-disk size of the chunks before c0 (what an earlier window
+// of the same output returned). Every new kept group ends past the earlier
+// window, so flushed(E) >= c0 for it and the running offsets of the new
+// chunks are all it needs: disk[i] = on-disk bytes before chunk c0 + i,
+// i in [0, c1 - c0]. The predicate is monotone in g, so each thread stops at
+// its first hit and the block takes the minimum.
+__global__ void __launch_bounds__(SIZE_CUT_BLOCK)
+k_size_cut(const uint64_t* ends, const uint8_t* keep, uint64_t g0, uint64_t g1, uint64_t base,
+           const uint32_t* csize, uint32_t c0, uint32_t c1, uint64_t disk0,
+           uint32_t chunk_len, uint64_t cap, uint64_t* disk, SizeCutResult* res) {
+    constexpr int NW = SIZE_CUT_BLOCK / WAVE;
+    __shared__ uint64_t sh_w[NW];
+    __shared__ uint64_t sh_carry;
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    if (threadIdx.x == 0) {
+        sh_carry = disk0;
+        disk[0] = disk0;
+    }
+    __syncthreads();
+    // ---- inclusive scan of csize[c] + 4 into running on-disk offsets ----
+    const uint32_t nc = c1 - c0;
+    for (uint32_t t0 = 0; t0 < nc; t0 += SIZE_CUT_BLOCK) {
+        uint32_t i = t0 + threadIdx.x;
+        uint64_t v = i < nc ? (uint64_t)csize[c0 + i] + 4 : 0;
+        for (int off = 1; off < WAVE; off <<= 1) {
+            uint64_t x = __shfl_up((unsigned long long)v, off);
+            if (lane >= off) v += x;
         }
+        if (lane == WAVE - 1) sh_w[wave] = v;
+        const uint64_t carry = sh_carry;
+        __syncthreads();
+        uint64_t woff = carry;
+        for (int w = 0; w < wave; w++) woff += sh_w[w];
+        if (i < nc) disk[i + 1] = woff + v;
+        if (threadIdx.x == SIZE_CUT_BLOCK - 1) sh_carry = woff + v;
+        __syncthreads();  // sh_w and sh_carry are free for the next tile
+    }
+    // disk[] was written by this block; the barriers above order it
+    // ---- est(E_g) per kept group, first one over the cap ----
+    uint64_t mine = SIZE_CUT_NONE;
+    for (uint64_t g = g0 + threadIdx.x; g < g1; g += SIZE_CUT_BLOCK) {
+        if (!keep[g]) continue;
+        uint64_t E = ends[g] - base;
+        uint64_t f = size_cut_flushed_chunks(E, chunk_len);
+        f = f < c0 ? c0 : (f > c1 ? c1 : f);  // in range by construction; never index outside disk[]
+        if (disk[f - c0] > cap) { mine = g; break; }
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        uint64_t x = __shfl_down((unsigned long long)mine, off);
+        mine = x < mine ? x : mine;
+    }
+    if (lane == 0) sh_w[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < NW; w++) mine = sh_w[w] < mine ? sh_w[w] : mine;
+        res->cut = mine;
+        res->disk = sh_carry;
     }
 }
 
-// output stats over the final OutParts/UnfCols (MetadataCollector semantics)
+// output stats over the final OutParts/UnfCols (MetadataCollector
+// semantics), groups [g0, n)
 __global__ void k_collect_rows(OutParts op, UnfCols out, uint64_t n, uint32_t n_cols,
                                uint32_t n_cpx, OutStats* st,
-                               uint32_t* tomb_ldts, uint32_t tomb_cap) {
+                               uint32_t* tomb_ldts, uint32_t tomb_cap, uint64_t g0 = 0) {
     __shared__ unsigned long long sh_parts, sh_rows, sh_cells, sh_mints, sh_maxts,
         sh_minldt, sh_maxldt, sh_haspdel;
     __shared__ unsigned int sh_minttl, sh_maxttl;
@@ -2579,7 +2731,7 @@ __global__ void k_collect_rows(OutParts op, UnfCols out, uint64_t n, uint32_t n_
         sh_maxttl = 0;
     }
     __syncthreads();
-    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < n && op.keep[g]) {
         auto lts = [&](int64_t ts) {
             if (ts == NO_TIMESTAMP) return;

@@ -132,6 +132,26 @@ typedef struct gpuc_job {
        every shard of n_output_shards. Inputs may have any supported length,
        each its own. */
     uint32_t output_chunk_length;
+
+    /* 0 == no size cap. Above 0 the output is split the way a Leveled
+       compaction's MaxSSTableSizeWriter splits it (sstable_size_in_mb; also
+       sstablesplit and --split-output): before a partition is appended, a new
+       sstable is started iff the current one already holds at least one
+       partition and its estimated on-disk bytes exceed max_output_bytes.
+       The estimate is the compressed size (payload + 4-byte CRC) of the
+       chunks already flushed, and a chunk is flushed when the next byte
+       arrives at a full buffer (CompactionAwareWriter.maybeSwitchWriter,
+       MaxSSTableSizeWriter.shouldSwitchWriterInCurrentLocation,
+       CompressedSequentialWriter.getEstimatedOnDiskBytesWritten). Every
+       output holds at least one partition; one partition larger than the cap
+       is an output of its own. Outputs are named like shards: the generation
+       of output_base, then +1, +2, ...; gpuc_result.n_outputs says how many.
+       The front of the pipeline runs once over the whole job. Allowed with
+       has_token_range, keep_ranges, overlaps, tombstone sources,
+       output_chunk_length and `da` inputs; with n_output_shards > 1 it is
+       GPUC_ERR_UNSUPPORTED (before any input byte is read). cancel_flag is
+       also polled between outputs. */
+    uint64_t max_output_bytes;
 } gpuc_job;
 
 typedef struct gpuc_result {
@@ -151,6 +171,8 @@ typedef struct gpuc_result {
     double dominant_kernel_ms;
     uint64_t dominant_kernel_launches;
     char error[256];
+    uint32_t n_outputs;                 /* sstables written: 1, the shard count, or
+                                           the outputs of a max_output_bytes split */
 } gpuc_result;
 
 /* One compaction task. Returns GPUC_OK or an error code (message in result->error). */
@@ -208,7 +230,7 @@ int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* error, size_
  * murmur3_128(2000)) hash (db/Digest.java:53-59) — to out_path instead of
  * an output sstable. The host feeds these to its MerkleTree
  * (Validator.add). Uses the same gpuc_job fields (now/gcBefore/overlaps);
- * sharding/tombstone-source/keep-range modes are rejected. */
+ * sharding/size-split/tombstone-source/keep-range modes are rejected. */
 int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
                   char* error, size_t error_len);
 
@@ -386,6 +408,19 @@ int gpuc_compress_buffer(const uint8_t* data, uint64_t len, uint32_t chunk_lengt
                          int32_t snappy, int32_t device, uint8_t* out, uint64_t out_cap,
                          uint64_t* out_len, uint64_t* offsets, uint32_t offsets_cap,
                          uint32_t* n_chunks, char* error, size_t error_len);
+
+/* Diagnostic: where the size-split writer (gpuc_job.max_output_bytes) would
+ * cut a stream of partitions, using the writer's own launches (chunk compress
+ * + k_size_cut, not a copy). part_ends[i] is the exclusive end offset of
+ * partition i in `data`, non-decreasing; an entry equal to its predecessor is
+ * a dropped (zero-byte) partition, which never carries a cut. cut_after
+ * receives the index of the last partition of every output but the final
+ * one. chunk_length as in gpuc_compress_buffer; max_output_bytes > 0. */
+int gpuc_plan_size_cuts(const uint8_t* data, uint64_t len,
+                        const uint64_t* part_ends, uint64_t n_parts,
+                        uint32_t chunk_length, int32_t snappy, uint64_t max_output_bytes,
+                        int32_t device, uint64_t* cut_after, uint64_t cut_cap, uint64_t* n_cuts,
+                        char* error, size_t error_len);
 
 /* library/build identification */
 const char* gpuc_version(void);
