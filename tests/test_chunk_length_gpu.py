@@ -86,6 +86,31 @@ def test_codec_direct_snappy(ca, chunk_len):
         assert got == want, (mode, len(got), len(want))
 
 
+@pytest.mark.parametrize("chunk_len", [1024, 65536])
+@pytest.mark.parametrize("codec", ["lz4", "snappy"])
+def test_codec_direct_edge_lengths(ca, codec, chunk_len):
+    """Whole-buffer lengths around the encoders' fixed limits (1 byte, the
+    12/13-byte minimum for a match) and around one chunk: a lone short chunk,
+    a full chunk, and a full chunk with a 1-, 12- or 13-byte tail chunk
+    (tests/native/chunklen_cases.h's lengths), every content mode."""
+    if codec == "snappy":
+        lib = ch.snappy()
+        if lib is None:
+            pytest.skip("libsnappy not present")
+        payload = lambda c: ch.snappy_payload(c, lib)
+    else:
+        payload = ch.lz4_payload
+    L = chunk_len
+    for n in (1, 12, 13, L - 1, L, L + 1, L + 12, L + 13):
+        for mode in range(8):
+            raw = ch.content(mode, n)
+            want, want_offs = ch.chunk_image(raw, L, payload)
+            got, offs = ca.compress_buffer(raw, chunk_length=L, snappy=codec == "snappy")
+            assert offs == want_offs, (n, mode, offs, want_offs)
+            assert got == want, (n, mode, len(got), len(want))
+    assert ca.compress_buffer(b"", chunk_length=L, snappy=codec == "snappy") == (b"", [])
+
+
 @pytest.mark.parametrize("chunk_len", [4096, 65536])
 def test_codec_snappy_image_through_oracle(ca, oracle_bin, tmp_path, chunk_len):
     """The GPU's Snappy image of an sstable's bytes, wrapped as that sstable,
