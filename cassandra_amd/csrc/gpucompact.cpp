@@ -592,6 +592,10 @@ static void parse_input(ParsedInput& in, const DevBuf& d_srcs, uint32_t n_srcs, 
     if (total)
         hipLaunchKernelGGL(k_widen_u32, grid, block, 0, stream, pc.row_count, pc.row_base, total);
     in.total_rows = exscan_u64(pc.row_base, total, stream);
+    // a partition that pass A rejected has no row count: the total is
+    // garbage then, and pass B would write past the rows it was given. The
+    // caller reads the same error word and reports it.
+    if (read_dev_error(d_error, stream)) return;
     in.rows.alloc(in.total_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
     if (!total) return;
     auto rows_pass = [&](const uint64_t* cpx_bases) {

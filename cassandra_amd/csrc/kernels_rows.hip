@@ -181,7 +181,8 @@ __global__ void k_parse_count(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t to
             uint32_t nv = ((uint32_t)base[pos] << 8) | base[pos + 1];
             pos += 2;
             if (kind == BK_STATIC || nv > sp.n_ck || (nv && sp.n_ck == 0)) { atomicExch(error, 15ull); return; }
-            if (nv == 0 && sp.n_ck != 0) { atomicExch(error, 16ull); return; }  // 0-value bound unsupported
+            // nv == 0 is the bound of a range open at that end (BOTTOM/TOP):
+            // kind and count only, no header and no values
             if (nv) {
                 uint64_t hdr = uvint_get(base, &pos);
                 if (hdr) { atomicExch(error, 17ull); return; }

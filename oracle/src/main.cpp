@@ -1,5 +1,6 @@
 // ORACLE CLI — test infrastructure only (see util.h header note).
-// Subcommands: roundtrip, dump, gen, compact, selftest, bench-compact.
+// Subcommands: roundtrip, dump, gen, compact, selftest, bench-compact,
+// dumpsst, fromdump.
 #include "sstable.h"
 #include "compact.h"
 #include "gen.h"
@@ -384,6 +385,21 @@ int main(int argc, char** argv) {
             // gpuc_flush_table parity harness)
             SSTable t = read_sstable(pos.at(0), false);
             write_memdump(t, pos.at(1));
+            return 0;
+        }
+        if (cmd == "fromdump") {
+            // fromdump <file.memdump> <outbase>: write a memdump (gen dump=1,
+            // dumpsst, or one authored by a test) as an sstable. Partitions
+            // are put in token order, as a flush would (stable: a dump that
+            // is already ordered keeps its order).
+            SSTable t = read_memdump(pos.at(0));
+            std::stable_sort(t.parts.begin(), t.parts.end(), [](const Partition& a, const Partition& b) {
+                return compare_decorated_key(a.token, a.key.data(), a.key.size(), b.token,
+                                             b.key.data(), b.key.size()) < 0;
+            });
+            WriterOut w = write_sstable(t, t.bti);
+            write_components(w, pos.at(1));
+            printf("wrote %zu partitions\n", t.parts.size());
             return 0;
         }
         if (cmd == "validate") {

@@ -58,6 +58,9 @@ int compare_typed(CqlType t, const bytes& a, const bytes& b) {
 // ---------------------------------------------------------------------------
 static void put_deletion_time(bytes& out, const DeletionTime& dt) {
     if (dt.live()) { out.push_back(0x80); return; }
+    // the sign bit of the first byte is the IS_LIVE flag: a negative
+    // markedForDeleteAt has no encoding here (the reader would reject it)
+    if (dt.mfda < 0) throw std::runtime_error("DeletionTime: negative markedForDeleteAt cannot be written in the oa format");
     put_be64(out, (uint64_t)dt.mfda);
     put_be32(out, dt.ldt);
 }
@@ -1442,6 +1445,164 @@ void write_memdump(const SSTable& t, const std::string& path) {
         }
     }
     write_file(path, o);
+}
+
+// read_memdump: the exact inverse of write_memdump. Test tooling authors
+// tables as memdumps (tests/authored_tables.py) and `fromdump` writes them
+// as sstables, so every malformed input is an error, never a guess.
+namespace {
+struct MdReader {
+    const bytes& d;
+    size_t pos = 0;
+    explicit MdReader(const bytes& b) : d(b) {}
+    void need(size_t n) const {
+        if (n > d.size() - pos)
+            throw std::runtime_error("memdump: truncated at byte " + std::to_string(pos));
+    }
+    uint8_t u8() { need(1); return d[pos++]; }
+    uint32_t u32() { need(4); uint32_t v = 0; for (int i = 3; i >= 0; i--) v = (v << 8) | d[pos + i]; pos += 4; return v; }
+    int32_t i32() { return (int32_t)u32(); }
+    uint64_t u64() { need(8); uint64_t v = 0; for (int i = 7; i >= 0; i--) v = (v << 8) | d[pos + i]; pos += 8; return v; }
+    int64_t i64() { return (int64_t)u64(); }
+    bytes blob() { uint32_t n = u32(); need(n); bytes b(d.begin() + pos, d.begin() + pos + n); pos += n; return b; }
+    [[noreturn]] void bad(const std::string& what) const {
+        throw std::runtime_error("memdump: " + what + " at byte " + std::to_string(pos));
+    }
+    CqlType type() {
+        uint8_t t = u8();
+        if (t > (uint8_t)CqlType::COUNTER) bad("unknown type ordinal " + std::to_string(t));
+        return (CqlType)t;
+    }
+    DeletionTime dt() { DeletionTime x; x.mfda = i64(); x.ldt = u32(); return x; }
+    // false == absent cell (flag byte 0)
+    bool cell(Cell& c) {
+        uint8_t cf = u8();
+        if (!cf) return false;
+        c.ts = i64();
+        c.ldt = u32();
+        c.ttl = i32();
+        c.value = blob();
+        // the flag bits are derived from the fields on write: check them
+        uint8_t want = 1 | (c.tombstone() ? 0 : 2) | (c.expiring() ? 4 : 0);
+        if (cf != want) bad("cell flags " + std::to_string(cf) + " contradict its fields");
+        return true;
+    }
+    Clustering clustering() {
+        Clustering c(u8());
+        for (auto& v : c) {
+            uint8_t s = u8();
+            if (s > ClusterVal::NUL) bad("bad clustering state");
+            v.state = (ClusterVal::State)s;
+            v.v = blob();
+        }
+        return c;
+    }
+    void row_head(uint8_t f, Row& r) {
+        r.live.ts = i64();
+        r.live.ttl = i32();
+        r.live.let = i64();
+        r.del = dt();
+        uint8_t want = 1 | (r.live.empty() ? 0 : 2) | (r.del.live() ? 0 : 4);
+        if (f != want) bad("row flags " + std::to_string(f) + " contradict its fields");
+    }
+};
+}  // namespace
+
+SSTable read_memdump(const std::string& path) {
+    bytes data = read_file(path);
+    MdReader r(data);
+    if (data.size() < 4 || memcmp(data.data(), "GMD2", 4) != 0)
+        throw std::runtime_error("memdump: bad magic in " + path);
+    r.pos = 4;
+    SSTable t;
+    t.generation = 1;
+    t.header.key_type = r.type();
+    uint32_t n_ck = r.u32();
+    for (uint32_t i = 0; i < n_ck; i++) t.header.clustering_types.push_back(r.type());
+    uint32_t n_static = r.u32();
+    for (uint32_t i = 0; i < n_static; i++) { bytes nm = r.blob(); t.header.static_cols.emplace_back(nm, r.type()); }
+    uint32_t n_reg = r.u32();
+    for (uint32_t i = 0; i < n_reg; i++) { bytes nm = r.blob(); t.header.regular_cols.emplace_back(nm, r.type()); }
+    uint8_t snappy = r.u8(), bti = r.u8();
+    if (snappy > 1 || bti > 1) r.bad("snappy/bti flag not 0 or 1");
+    t.comp.algo = snappy ? Compressor::SNAPPY : Compressor::LZ4;
+    t.bti = bti != 0;
+    t.column_index_size = r.u32();
+    t.header.stats.min_ts = r.i64();
+    t.header.stats.min_ldt = r.i64();
+    t.header.stats.min_ttl = r.i32();
+    uint64_t n_parts = r.u64();
+    const auto& regs = t.header.regular_cols;
+    bool any_cpx = false;
+    for (auto& c : regs) any_cpx |= is_complex_type(c.second);
+    for (uint64_t pi = 0; pi < n_parts; pi++) {
+        Partition p;
+        p.key = r.blob();
+        p.set_token();
+        p.del = r.dt();
+        if (n_static) {
+            uint8_t f = r.u8();
+            if (f) {
+                Row& sr = p.static_row;
+                sr.static_flag = true;
+                r.row_head(f, sr);
+                sr.cells.assign(n_static, std::nullopt);
+                for (uint32_t i = 0; i < n_static; i++) {
+                    Cell c;
+                    if (r.cell(c)) sr.cells[i] = std::move(c);
+                }
+            }
+        }
+        uint32_t n_items = r.u32();
+        for (uint32_t ui = 0; ui < n_items; ui++) {
+            Unfiltered u;
+            uint8_t tag = r.u8();
+            if (tag == 0) {
+                u.kind = Unfiltered::ROW;
+                Row& row = u.row;
+                row.clustering = r.clustering();
+                row.cells.assign(regs.size(), std::nullopt);
+                if (any_cpx) row.complex.assign(regs.size(), std::nullopt);
+                r.row_head(r.u8(), row);
+                for (size_t i = 0; i < regs.size(); i++) {
+                    if (regs[i].second == CqlType::MAP_BB) {
+                        uint8_t has = r.u8();
+                        if (has > 1) r.bad("complex presence flag not 0 or 1");
+                        if (!has) continue;
+                        ComplexData cd;
+                        cd.del = r.dt();
+                        uint32_t nc = r.u32();
+                        for (uint32_t e = 0; e < nc; e++) {
+                            Cell c;
+                            if (!r.cell(c)) r.bad("absent cell inside complex data");
+                            c.path = r.blob();
+                            cd.cells.push_back(std::move(c));
+                        }
+                        row.complex[i] = std::move(cd);
+                    } else {
+                        Cell c;
+                        if (r.cell(c)) row.cells[i] = std::move(c);
+                    }
+                }
+            } else if (tag == 1) {
+                u.kind = Unfiltered::MARKER;
+                uint8_t k = r.u8();
+                if (k > EXCL_START || k == STATIC_K || k == CLUSTERING_K) r.bad("bad marker kind");
+                u.marker.kind = (BoundKind)k;
+                u.marker.values = r.clustering();
+                u.marker.end_dt = r.dt();
+                u.marker.start_dt = r.dt();
+            } else {
+                r.bad("bad unfiltered tag " + std::to_string(tag));
+            }
+            p.items.push_back(std::move(u));
+        }
+        t.parts.push_back(std::move(p));
+    }
+    if (r.pos != data.size())
+        throw std::runtime_error("memdump: " + std::to_string(data.size() - r.pos) +
+                                 " trailing bytes after " + std::to_string(n_parts) + " partitions");
+    return t;
 }
 
 }  // namespace oracle

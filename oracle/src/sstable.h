@@ -281,6 +281,10 @@ WriterOut write_sstable(const SSTable& t, bool bti = false);
 void write_components(const WriterOut& w, const std::string& base);
 // memtable-dump interchange for gpuc_flush_table parity (format ours; see .cpp)
 void write_memdump(const SSTable& t, const std::string& path);
+// exact inverse of write_memdump; throws on bad magic, truncation, trailing
+// bytes, or flag bytes that contradict the fields they summarize. Tokens are
+// set (Murmur3); partition order is the file's.
+SSTable read_memdump(const std::string& path);
 
 // serialize one partition into `out` (Data.db stream) and append its Index.db
 // entry to `index_out`. Exposed for round-trip tests.
