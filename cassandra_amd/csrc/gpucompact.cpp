@@ -555,6 +555,23 @@ struct DevSchema {
     }
 };
 
+// a source's own header (its counts and its maps into the union) in its SrcDesc2
+static void set_src_columns(SrcDesc2& sd, const SourceColumns& sc) {
+    sd.n_cols = sc.n_cols;
+    sd.n_cpx = sc.n_cpx;
+    sd.n_static = sc.n_static;
+    std::copy(sc.col_map.begin(), sc.col_map.end(), sd.col_map);
+    std::copy(sc.cpx_map.begin(), sc.cpx_map.end(), sd.cpx_map);
+    std::copy(sc.static_map.begin(), sc.static_map.end(), sd.static_map);
+}
+// the single-source callers: the source's header IS the schema
+static void set_src_identity(SrcDesc2& sd, const SchemaParams& sch) {
+    sd.n_cols = sch.n_cols;
+    sd.n_cpx = sch.n_cpx;
+    sd.n_static = sch.n_static;
+    for (uint32_t i = 0; i < 63; i++) sd.col_map[i] = sd.cpx_map[i] = sd.static_map[i] = (uint8_t)i;
+}
+
 // parsed input: per-partition columns, static rows, the unfiltered arena and
 // the complex-cell bases
 struct ParsedInput {
@@ -1606,7 +1623,9 @@ struct CompactSetup {
     std::vector<std::vector<uint64_t>> entry_offs;  // Index.db entry byte offsets
     std::vector<std::vector<bti::bytes>> bti_prefixes;  // da: trie separator per partition
     std::vector<size_t> comp_file_sz;
-    HostSchema schema;                   // resolved from stats[0]
+    // one schema for the job: the union of the compacting inputs' headers
+    // (the output header), and every source's own columns mapped into it
+    JobSchema js;
     bool bti = false;                    // inputs are `da` (trie-indexed)
     // unsharded fast path: whole-file Data.db reads started during index
     // parse as ordered STRIPES per source (compact_one adopts them when its
@@ -1793,11 +1812,12 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             srcs[s].min_ldt = stats[s].hdr_min_ldt;
             srcs[s].min_ttl = stats[s].hdr_min_ttl;
             srcs[s].rec_base = (uint32_t)total_parts;
+            set_src_columns(srcs[s], su.js.src[s]);
             total_parts += srcs[s].n_parts;
         }
         if (total_parts > 0xFFFFFFFFull) throw std::runtime_error("too many partitions for one job");
         DevSchema dsch;
-        SchemaParams sch = dsch.upload(su.schema, stream);
+        SchemaParams sch = dsch.upload(su.js.schema, stream);
         DevBuf d_srcs, d_recs_a, d_recs_b, d_rows_in;
         d_srcs.alloc(srcs.size() * sizeof(SrcDesc2));
         HIP_CHECK(hipMemcpyAsync(d_srcs.p, srcs.data(), srcs.size() * sizeof(SrcDesc2),
@@ -2086,12 +2106,12 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             // written sstable (k_validate_digest; Validator.rowHash)
             bytes names;
             std::vector<uint32_t> noff;
-            for (auto& [nm, t2] : stats[0].regular_cols) {
+            for (auto& [nm, t2] : su.js.header.regular_cols) {
                 (void)t2;
                 noff.push_back((uint32_t)names.size());
                 names.insert(names.end(), nm.begin(), nm.end());
             }
-            for (auto& [nm, t2] : stats[0].static_cols) {
+            for (auto& [nm, t2] : su.js.header.static_cols) {
                 (void)t2;
                 noff.push_back((uint32_t)names.size());
                 names.insert(names.end(), nm.begin(), nm.end());
@@ -2106,8 +2126,8 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             ValidateParams vpar{};
             vpar.names = d_names.as<uint8_t>();
             vpar.name_off = d_noff.as<uint32_t>();
-            vpar.n_reg = (uint32_t)stats[0].regular_cols.size();
-            vpar.n_static = (uint32_t)stats[0].static_cols.size();
+            vpar.n_reg = (uint32_t)su.js.header.regular_cols.size();
+            vpar.n_static = (uint32_t)su.js.header.static_cols.size();
             vpar.counters = sch.counters;
             vpar.n_cpx = sch.n_cpx;
             vpar.n_ck = sch.n_ck;
@@ -2150,12 +2170,12 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 in_unc += cinfos[s].data_len;
             }
             w = write_sstables_size_split(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
-                                          tomb_cap, stats[0], oopt, job->max_output_bytes,
+                                          tomb_cap, su.js.header, oopt, job->max_output_bytes,
                                           in_unc ? (double)in_comp / (double)in_unc : 1.0,
                                           [&]() { check_cancel(job); }, stream);
         } else {
             w = write_sstable_device(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
-                                     tomb_cap, stats[0], oopt, stream);
+                                     tomb_cap, su.js.header, oopt, stream);
         }
         TR("writer done");
         {
@@ -2321,8 +2341,6 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
     for (int s = 0; s < k; s++) {
         const std::string& base = su.in_bases[s];
         auto& st = su.stats[s];
-        if (st.regular_cols.empty() || st.regular_cols.size() > 63)
-            throw std::runtime_error("1..63 regular columns supported");
         if (!st.partitioner.empty() && st.partitioner.find("Murmur3") == std::string::npos)
             throw std::runtime_error("Murmur3Partitioner required");
         size_t sl = base.rfind('/');
@@ -2330,7 +2348,7 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
         size_t a = name.find('-'), b2 = name.find('-', a + 1);
         su.generations[s] = std::stoull(name.substr(a + 1, b2 - a - 1));
     }
-    su.schema = resolve_schema(su.stats[0]);
+    su.js = resolve_job_schema(su.stats, su.k_data);
     if (su.bti) {
         // positions collected from the tries above; append the end sentinel
         for (int s = 0; s < k; s++) su.positions[s].push_back(su.cinfos[s].data_len);
@@ -2627,6 +2645,7 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         src.min_ldt = st.hdr_min_ldt;
         src.min_ttl = st.hdr_min_ttl;
         src.rec_base = 0;
+        set_src_identity(src, sch);
         DevBuf d_src;
         d_src.alloc(sizeof(src));
         HIP_CHECK(hipMemcpyAsync(d_src.p, &src, sizeof(src), hipMemcpyHostToDevice, stream));
@@ -2754,6 +2773,7 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         src.min_ldt = st.hdr_min_ldt;
         src.min_ttl = st.hdr_min_ttl;
         src.rec_base = 0;
+        set_src_identity(src, sch);
         DevBuf d_src;
         d_src.alloc(sizeof(src));
         HIP_CHECK(hipMemcpyAsync(d_src.p, &src, sizeof(src), hipMemcpyHostToDevice, stream));

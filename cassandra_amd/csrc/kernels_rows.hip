@@ -24,7 +24,9 @@ __device__ inline void tomb_push(OutStats* st, uint32_t* ldts, uint32_t cap, uin
     if (i < cap) ldts[i] = ldt;
 }
 
-// schema/runtime constants shared by the general kernels
+// schema/runtime constants shared by the general kernels. In a compaction job
+// this is the UNION of the inputs' headers; what a single source's own header
+// lists is in its SrcDesc2.
 struct SchemaParams {
     uint32_t n_ck;           // clustering columns (0..32)
     const int32_t* ck_w;     // per clustering column: 4/8 fixed or -1 variable
@@ -115,6 +117,14 @@ struct SrcDesc2 {
     int64_t min_ts, min_ldt;
     int32_t min_ttl;
     uint32_t rec_base;         // partition index base in the concatenated arrays
+    // this source's OWN serialization header (the inputs of one job may list
+    // different columns; SchemaParams describes their union): its counts, and
+    // per own simple / complex / static column the union index. Each map is
+    // strictly increasing (resolve_job_schema), so a source's columns are a
+    // subsequence of the union's. Subset-bitmap bit j is own simple column j,
+    // bit n_cols + x own complex column x.
+    uint32_t n_cols, n_cpx, n_static;
+    uint8_t col_map[63], cpx_map[63], static_map[63];
 };
 
 __global__ void k_parse_count(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t total,
@@ -159,8 +169,8 @@ __global__ void k_parse_count(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t to
     pc.pdel_mfda[gi] = pdm;
     pc.pdel_ldt[gi] = pdl;
 
-    // static row slot (always present on disk when the schema has statics)
-    if (sp.n_static) {
+    // static row slot (always present on disk when THIS source's header has statics)
+    if (sd.n_static) {
         uint8_t f = base[pos++];
         if (!(f & 0x80) || base[pos] != 0x01) { atomicExch(error, 18ull); return; }
         pos++;
@@ -170,11 +180,12 @@ __global__ void k_parse_count(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t to
     }
 
     // skip-walk the unfiltereds
+    const uint32_t src_cpx = sd.n_cpx;
     uint32_t count = 0;
     while (true) {
         uint8_t flags = base[pos++];
         if (flags & 0x01) break;  // END_OF_PARTITION
-        if ((flags & 0x80) || ((flags & 0x40) && !sp.n_cpx)) { atomicExch(error, 12ull); return; }  // extension / unexpected complex
+        if ((flags & 0x80) || ((flags & 0x40) && !src_cpx)) { atomicExch(error, 12ull); return; }  // extension / unexpected complex
         if (flags & 0x02) {
             // marker: kind, u16 size, values
             uint8_t kind = base[pos++];
@@ -228,11 +239,21 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
     pos += 2 + klen;
     pos += (base[pos] & 0x80) ? 1 : 12;
 
+    // The column loops below walk the UNION's columns with a cursor over this
+    // source's own: union column c is own column j iff map[j] == c (the maps
+    // increase strictly), and then subset-bitmap bit j speaks for it. Every
+    // other union slot is written absent.
     if (sp.n_static) {
-        uint8_t flags = base[pos++];
-        pos++;  // extended flags byte (IS_STATIC, validated in pass A)
-        uvint_get(base, &pos);  // size
-        uvint_get(base, &pos);  // prev
+        // a source whose header has no statics has no static slot on disk:
+        // its partitions get an empty static row
+        const uint32_t src_static = sd.n_static;
+        uint8_t flags = 0x20;
+        if (src_static) {
+            flags = base[pos++];
+            pos++;  // extended flags byte (IS_STATIC, validated in pass A)
+            uvint_get(base, &pos);  // size
+            uvint_get(base, &pos);  // prev
+        }
         uint8_t pf = 0;
         int64_t lts = NO_TIMESTAMP, llet = NO_DELETION_TIME, rdm = INT64_MIN;
         int32_t lttl = 0;
@@ -250,9 +271,15 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
         uint64_t missing = 0;
         if (!(flags & 0x20)) missing = uvint_get(base, &pos);
         bool any_cell = false;
+        uint32_t sj = 0;
         for (uint32_t c = 0; c < sp.n_static; c++) {
             uint64_t oc = (uint64_t)gi * sp.n_static + c;
-            if (missing & (1ULL << c)) { pc.st.cell_flags[oc] = 0; continue; }
+            bool here = false;
+            if (sj < src_static && sd.static_map[sj] == c) {
+                here = !(missing & (1ULL << sj));
+                sj++;
+            }
+            if (!here) { pc.st.cell_flags[oc] = 0; continue; }
             any_cell = true;
             uint8_t cfl = CELLF_PRESENT;
             uint8_t cf = base[pos++];
@@ -294,6 +321,7 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
     uint64_t cpx_cur = (sp.n_cpx && cpx_base) ? cpx_base[gi] : 0;
     uint32_t cpx_seen = 0;
     unsigned long long rows_local = 0;
+    const uint32_t src_cols = sd.n_cols, src_cpx = sd.n_cpx;
     while (true) {
         uint8_t flags = base[pos++];
         if (flags & 0x01) break;
@@ -385,9 +413,15 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
             // columns subset (Columns.serializeSubset: vint bitmap of MISSING)
             uint64_t missing = 0;
             if (!(flags & 0x20)) missing = uvint_get(base, &pos);
+            uint32_t sj = 0;
             for (uint32_t c = 0; c < sp.n_cols; c++) {
                 uint64_t oc = o * sp.n_cols + c;
-                if (missing & (1ULL << c)) {
+                bool here = false;
+                if (sj < src_cols && sd.col_map[sj] == c) {
+                    here = !(missing & (1ULL << sj));
+                    sj++;
+                }
+                if (!here) {
                     rc.cell_flags[oc] = 0;
                     continue;
                 }
@@ -417,10 +451,15 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
                 rc.val_addr[oc] = vaddr;
                 rc.val_len[oc] = vlen;
             }
-            // ---- complex columns (bit sp.n_cols + x of the subset bitmap) ----
+            // ---- complex columns (bit src_cols + own index of the subset bitmap) ----
+            uint32_t sx = 0;
             for (uint32_t x = 0; x < sp.n_cpx; x++) {
                 uint64_t ox = o * sp.n_cpx + x;
-                bool xp = !(missing & (1ULL << (sp.n_cols + x)));
+                bool xp = false;
+                if (sx < src_cpx && sd.cpx_map[sx] == x) {
+                    xp = !(missing & (1ULL << (src_cols + sx)));
+                    sx++;
+                }
                 rc.cpx_present[ox] = xp;
                 rc.cpx_del_mfda[ox] = INT64_MIN;
                 rc.cpx_del_ldt[ox] = LDT_NONE_U32;

@@ -5,6 +5,7 @@
 #pragma once
 #include "codec.h"
 
+#include <algorithm>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -291,7 +292,9 @@ struct HostSchema {
     uint32_t n_cpx = 0;                 // trailing complex (map<blob,blob>) columns
     bool counters = false;              // counter table (every column CounterColumnType)
 };
-// The one resolver: rejects every layout the engine cannot walk.
+// The resolver of ONE header: rejects every layout the engine cannot walk.
+// Scrub and verify call it on their single input; a compaction job goes
+// through resolve_job_schema below, which calls it on the union header.
 inline HostSchema resolve_schema(const HStatistics& st) {
     HostSchema hs;
     const auto& rcols = st.regular_cols;
@@ -343,6 +346,116 @@ inline HostSchema resolve_schema(const HStatistics& st) {
     if (hs.ck_widths.size() > 32)
         throw std::runtime_error("at most 32 clustering columns supported");
     return hs;
+}
+
+// ---------------------------------------------------------------------------
+// job schema: the inputs of one job may list different columns. The output
+// header is the union of the compacting inputs' columns in Columns order, as
+// SerializationHeader.make builds it; each source keeps its own header for the
+// parse walk and maps its columns into the union by name.
+// ---------------------------------------------------------------------------
+struct SourceColumns {
+    uint32_t n_cols = 0, n_cpx = 0, n_static = 0;  // of this source's own header
+    // source simple column j / complex column x / static column j -> union index
+    std::vector<uint8_t> col_map, cpx_map, static_map;
+};
+struct JobSchema {
+    HStatistics header;  // stats[0] with the two column lists replaced by the union
+    HostSchema schema;   // resolve_schema(header)
+    std::vector<SourceColumns> src;  // one per source, tombstone sources included
+};
+inline std::string column_label(const bytes& name) {
+    return "'" + std::string((const char*)name.data(), name.size()) + "'";
+}
+// stats[0..k_data) are the compacting inputs, the rest tombstone sources (they
+// shadow, but add no column to the output header). Throws unsupported_error,
+// naming the column, for every combination of headers the engine cannot map.
+inline JobSchema resolve_job_schema(const std::vector<HStatistics>& stats, int k_data) {
+    using Cols = std::vector<std::pair<bytes, std::string>>;
+    if (k_data < 1 || (size_t)k_data > stats.size()) throw std::runtime_error("no compacting input");
+    const std::string map_prefix = "org.apache.cassandra.db.marshal.MapType(";
+    auto is_complex = [&](const std::string& t) { return t.compare(0, map_prefix.size(), map_prefix) == 0; };
+    for (size_t s = 1; s < stats.size(); s++) {
+        if (stats[s].key_type != stats[0].key_type)
+            throw unsupported_error("inputs differ in their partition key type: " +
+                                    stats[0].key_type + " against " + stats[s].key_type);
+        if (stats[s].clustering_types != stats[0].clustering_types)
+            throw unsupported_error("inputs differ in their clustering types");
+    }
+    JobSchema js;
+    js.header = stats[0];
+    bool same = true;
+    for (int s = 1; s < k_data; s++)
+        same = same && stats[s].regular_cols == stats[0].regular_cols &&
+               stats[s].static_cols == stats[0].static_cols;
+    if (!same) {
+        // Columns order: simple columns by name, then complex columns by name;
+        // names compare as unsigned bytes, a prefix before its extensions
+        // (std::vector<uint8_t>::operator<)
+        auto unite = [&](Cols HStatistics::*list) {
+            Cols u;
+            for (int s = 0; s < k_data; s++)
+                for (auto& c : stats[s].*list) {
+                    auto it = u.begin();
+                    while (it != u.end() && it->first != c.first) ++it;
+                    if (it == u.end()) u.push_back(c);
+                    else if (it->second != c.second)
+                        throw unsupported_error("column " + column_label(c.first) + " is " +
+                                                it->second + " in one input and " + c.second +
+                                                " in another");
+                }
+            std::stable_sort(u.begin(), u.end(), [&](const auto& a, const auto& b) {
+                bool ca = is_complex(a.second), cb = is_complex(b.second);
+                return ca != cb ? cb : a.first < b.first;
+            });
+            return u;
+        };
+        js.header.regular_cols = unite(&HStatistics::regular_cols);
+        js.header.static_cols = unite(&HStatistics::static_cols);
+    }
+    if (js.header.regular_cols.empty())
+        throw std::runtime_error("1..63 regular columns supported");
+    js.schema = resolve_schema(js.header);  // the existing rejections, on the union
+    const uint32_t n_simple = (uint32_t)js.schema.col_fixed.size();
+    // every source's header must be a subsequence of the union: then bit j of
+    // its column-subset bitmaps is its own column j, and a row's complex
+    // segments stay end to end in union order
+    auto map_list = [&](size_t s, const Cols& own, const Cols& uni, const char* what) {
+        std::vector<uint8_t> m;
+        size_t last = 0;
+        for (auto& c : own) {
+            size_t u = 0;
+            while (u < uni.size() && uni[u].first != c.first) u++;
+            if (u == uni.size())
+                throw unsupported_error(std::string("tombstone source has ") + what + " column " +
+                                        column_label(c.first) + " that no compacting input has");
+            if (uni[u].second != c.second)
+                throw unsupported_error("column " + column_label(c.first) + " is " +
+                                        uni[u].second + " in one input and " + c.second +
+                                        " in another");
+            if (!m.empty() && u <= last)
+                throw unsupported_error(std::string("header of input ") + std::to_string(s) +
+                                        " is not in Columns order at " + what + " column " +
+                                        column_label(c.first));
+            m.push_back((uint8_t)u);
+            last = u;
+        }
+        return m;
+    };
+    js.src.resize(stats.size());
+    for (size_t s = 0; s < stats.size(); s++) {
+        SourceColumns& sc = js.src[s];
+        std::vector<uint8_t> reg = map_list(s, stats[s].regular_cols, js.header.regular_cols, "regular");
+        for (uint8_t u : reg) {
+            if (u < n_simple) sc.col_map.push_back(u);
+            else sc.cpx_map.push_back((uint8_t)(u - n_simple));
+        }
+        sc.static_map = map_list(s, stats[s].static_cols, js.header.static_cols, "static");
+        sc.n_cols = (uint32_t)sc.col_map.size();
+        sc.n_cpx = (uint32_t)sc.cpx_map.size();
+        sc.n_static = (uint32_t)sc.static_map.size();
+    }
+    return js;
 }
 
 }  // namespace gpuc

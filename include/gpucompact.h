@@ -13,7 +13,23 @@
  * Chunk lengths above 64 KiB are GPUC_ERR_UNSUPPORTED (liblz4 leaves its
  * byU16 table at 65547 input bytes and snappy splits into several 64 KiB
  * fragments: different algorithms); a zero or non-power-of-two length in a
- * CompressionInfo.db is GPUC_ERR_FORMAT. The Java host above the seam
+ * CompressionInfo.db is GPUC_ERR_FORMAT.
+ *
+ * The inputs of one job may list different columns in their serialization
+ * headers (sstables older than an ALTER TABLE ... ADD, flushes that held only
+ * some columns). Each input is parsed under its own header; the output header
+ * is the union of the compacting inputs' regular and static columns in
+ * Columns order (simple columns by name, then complex columns by name; names
+ * compare as unsigned bytes), as SerializationHeader.make builds it. Inputs
+ * that all carry the same header keep it as it stands. Tombstone sources are
+ * mapped into that union by name and add no column to it. The column limits
+ * above apply to the union. GPUC_ERR_UNSUPPORTED, with the column named and
+ * before any Data.db byte is parsed, when: a column name carries different
+ * types in two inputs; key or clustering types differ between inputs;
+ * headers differ and one of them is not in Columns order; a tombstone source
+ * has a column that no compacting input has. A job carries no table metadata:
+ * a dropped column's cells are not filtered by drop time, and the column stays
+ * in the output header. The Java host above the seam
  * (strategies, CompactionManager, LifecycleTransaction, metrics) is
  * unchanged and binds these entry points via JNI/Panama.
  *
