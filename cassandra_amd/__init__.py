@@ -184,6 +184,11 @@ def load_library(path=None):
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
             ctypes.c_char_p, ctypes.c_size_t]
         lib.gpuc_plan_size_cuts.restype = ctypes.c_int
+    if hasattr(lib, "gpuc_validate_merkle"):  # absent in frozen A/B probe builds
+        lib.gpuc_validate_merkle.argtypes = [
+            ctypes.POINTER(GpucJob), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+            ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+        lib.gpuc_validate_merkle.restype = ctypes.c_int
     lib.gpuc_version.restype = ctypes.c_char_p
     lib.gpuc_device_count.restype = ctypes.c_int
     _lib = lib
@@ -799,6 +804,114 @@ def validate(input_bases, out_path, now_sec=1800000000, gc_before=INT64_MIN,
     if rc != 0:
         raise GpuCompactError(f"gpuc_validate rc={rc}: {err.value.decode(errors='replace')}")
     return n.value
+
+
+class GpucMerkleSpec(ctypes.Structure):
+    _fields_ = [
+        ("n_trees", ctypes.c_uint32),
+        ("tree_left", ctypes.POINTER(ctypes.c_int64)),
+        ("leaf_begin", ctypes.POINTER(ctypes.c_uint32)),
+        ("leaf_right", ctypes.POINTER(ctypes.c_int64)),
+    ]
+
+
+def validate_merkle(input_bases, trees, now_sec=1800000000, gc_before=INT64_MIN,
+                    overlaps=None, token_range=None, device=0, never_purge=False,
+                    n_output_shards=1, max_output_bytes=0, tombstone_sources=None,
+                    keep_ranges=None, raw_spec=None, n_leaves=None,
+                    want_leaf_partitions=True, want_n_partitions=True):
+    """VALIDATION compaction reduced to Merkle-tree leaves on the device
+    (gpuc_validate_merkle): the digests of validate(), XORed into the leaf
+    that holds each partition's token.
+
+    trees: list of (left_exclusive, [leaf_right, ...]), ascending and
+      disjoint; leaf i covers (previous right or left_exclusive, leaf_right[i]].
+    token_range: (lo, hi) inclusive, intersected with the trees.
+    n_output_shards / max_output_bytes / tombstone_sources / keep_ranges are
+      the modes the library rejects; they are passed through so that it can.
+    Returns (list of 32-byte hashes, list of partition counts, n_partitions)
+    in flat leaf order; counts is None with want_leaf_partitions=False and
+    n_partitions None with want_n_partitions=False (NULL out pointers).
+
+    raw_spec: escape hatch that skips `trees`: (n_trees, tree_left,
+      leaf_begin, leaf_right), the three arrays as lists or None (== NULL),
+      handed to the library UNCHECKED (nothing here validates a spec: refusing
+      a bad one is the library's job); raw_spec=None itself passes a NULL
+      spec when `trees` is None too. n_leaves sizes the output buffers then
+      (default: the last leaf_begin entry, or 1).
+    """
+    lib = load_library()
+    job = GpucJob()
+    arr = (ctypes.c_char_p * len(input_bases))(*[b.encode() for b in input_bases])
+    job.input_bases = arr
+    job.n_inputs = len(input_bases)
+    job.output_base = b"/unused"
+    job.now_sec = now_sec
+    job.gc_before = gc_before
+    job.never_purge = 1 if never_purge else 0
+    if overlaps:
+        ovr = (GpucPurgeRange * len(overlaps))()
+        for i, (lo, hi, ts) in enumerate(overlaps):
+            ovr[i].token_lo, ovr[i].token_hi, ovr[i].min_timestamp = lo, hi, ts
+        job.overlaps = ovr
+        job.n_overlaps = len(overlaps)
+    if token_range is not None:
+        job.has_token_range = 1
+        job.token_lo, job.token_hi = token_range
+    job.device = device
+    job.n_output_shards = n_output_shards
+    job.max_output_bytes = max_output_bytes
+    if tombstone_sources:
+        tarr = (ctypes.c_char_p * len(tombstone_sources))(*[b.encode() for b in tombstone_sources])
+        job.tombstone_source_bases = tarr
+        job.n_tomb_sources = len(tombstone_sources)
+    if keep_ranges:
+        kr = (GpucPurgeRange * len(keep_ranges))()
+        for i, (lo, hi) in enumerate(keep_ranges):
+            kr[i].token_lo, kr[i].token_hi = lo, hi
+        job.keep_ranges = kr
+        job.n_keep_ranges = len(keep_ranges)
+
+    if trees is not None:
+        lefts = [t[0] for t in trees]
+        begin = [0]
+        rights = []
+        for _, rs in trees:
+            rights.extend(rs)
+            begin.append(len(rights))
+        raw_spec = (len(trees), lefts, begin, rights)
+    spec_ref = None
+    if raw_spec is not None:
+        n_trees, lefts, begin, rights = raw_spec
+        spec = GpucMerkleSpec()
+        spec.n_trees = n_trees
+        keep_alive = []
+        for field, ctype, vals in (("tree_left", ctypes.c_int64, lefts),
+                                   ("leaf_begin", ctypes.c_uint32, begin),
+                                   ("leaf_right", ctypes.c_int64, rights)):
+            if vals is None:
+                continue  # stays NULL
+            buf = (ctype * max(len(vals), 1))(*vals)
+            keep_alive.append(buf)
+            setattr(spec, field, ctypes.cast(buf, ctypes.POINTER(ctype)))
+        spec_ref = ctypes.byref(spec)
+        if n_leaves is None:
+            n_leaves = begin[-1] if begin and trees is not None else 1
+    if n_leaves is None:
+        n_leaves = 1
+    hashes = (ctypes.c_uint8 * (32 * n_leaves))()
+    counts = (ctypes.c_uint64 * n_leaves)() if want_leaf_partitions else None
+    n = ctypes.c_uint64(0)
+    err = ctypes.create_string_buffer(256)
+    rc = lib.gpuc_validate_merkle(ctypes.byref(job), spec_ref, hashes, counts,
+                                  ctypes.byref(n) if want_n_partitions else None, err, 256)
+    if rc != 0:
+        raise GpuCompactError(
+            f"gpuc_validate_merkle rc={rc}: {err.value.decode(errors='replace')}")
+    raw = bytes(hashes)
+    return ([raw[32 * i:32 * i + 32] for i in range(n_leaves)],
+            list(counts) if counts is not None else None,
+            n.value if want_n_partitions else None)
 
 
 def generate(

@@ -63,6 +63,15 @@ static bool g_trace = getenv("GPUC_TRACE") != nullptr;
 // validation mode: set by gpuc_validate around its gpuc_compact-shaped run
 static thread_local const char* g_validate_out = nullptr;
 static thread_local uint64_t g_validate_count = 0;
+// Merkle-leaf validation: set by gpuc_validate_merkle around its run, in place
+// of g_validate_out. The spec is checked before it gets here.
+struct MerkleRun {
+    const gpuc_merkle_spec* spec;
+    uint8_t* leaf_hash;         // n_leaves * 32, out
+    uint64_t* leaf_partitions;  // n_leaves, out; may be NULL
+    uint64_t n_partitions;      // out: sum of the leaf counts
+};
+static thread_local MerkleRun* g_merkle = nullptr;
 static double g_trace_t0 = 0;
 static double trace_wall() {
     struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -1663,6 +1672,42 @@ static inline void check_cancel(const gpuc_job* job) {
     if (job->cancel_flag && *job->cancel_flag) throw cancelled_error();
 }
 
+// k_validate_digest's parameters: the output header's column names, packed
+// regular then static, on the device. Holds the host staging of its async
+// copies, so it lives until the stream is next synchronised.
+struct ValidateNames {
+    bytes names;
+    std::vector<uint32_t> noff;
+    DevBuf d_names, d_noff;
+    ValidateParams upload(const TableTypes& header, const SchemaParams& sch, hipStream_t stream) {
+        for (auto& [nm, t2] : header.regular_cols) {
+            (void)t2;
+            noff.push_back((uint32_t)names.size());
+            names.insert(names.end(), nm.begin(), nm.end());
+        }
+        for (auto& [nm, t2] : header.static_cols) {
+            (void)t2;
+            noff.push_back((uint32_t)names.size());
+            names.insert(names.end(), nm.begin(), nm.end());
+        }
+        noff.push_back((uint32_t)names.size());
+        d_names.alloc(names.size() + 8);
+        d_noff.alloc(noff.size() * 4);
+        HIP_CHECK(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, stream));
+        ValidateParams vpar{};
+        vpar.names = d_names.as<uint8_t>();
+        vpar.name_off = d_noff.as<uint32_t>();
+        vpar.n_reg = (uint32_t)header.regular_cols.size();
+        vpar.n_static = (uint32_t)header.static_cols.size();
+        vpar.counters = sch.counters;
+        vpar.n_cpx = sch.n_cpx;
+        vpar.n_ck = sch.n_ck;
+        vpar.ck_w = sch.ck_w;
+        return vpar;
+    }
+};
+
 static void compact_one(const gpuc_job* job, const CompactSetup& su,
                         const std::vector<std::pair<uint32_t, uint32_t>>& pr,
                         const std::string& out_base_str, int wslot,
@@ -1941,6 +1986,29 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             pp.n_keep_ranges = job->n_keep_ranges;
             pp.invert_ranges = job->invert_ranges;
         }
+        // Merkle-leaf validation: assign every group its leaf now, so that
+        // reconcile drops the partitions of no tree before merging them
+        DevBuf d_mk_left, d_mk_begin, d_mk_right, d_group_leaf;
+        uint32_t mk_leaves = 0;
+        if (g_merkle) {
+            const gpuc_merkle_spec& ms = *g_merkle->spec;
+            mk_leaves = ms.leaf_begin[ms.n_trees];
+            d_mk_left.alloc((uint64_t)ms.n_trees * 8);
+            d_mk_begin.alloc(((uint64_t)ms.n_trees + 1) * 4);
+            d_mk_right.alloc((uint64_t)mk_leaves * 8);
+            d_group_leaf.alloc(n_groups * 4 + 4);
+            HIP_CHECK(hipMemcpyAsync(d_mk_left.p, ms.tree_left, (uint64_t)ms.n_trees * 8, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_mk_begin.p, ms.leaf_begin, ((uint64_t)ms.n_trees + 1) * 4, hipMemcpyHostToDevice, stream));
+            HIP_CHECK(hipMemcpyAsync(d_mk_right.p, ms.leaf_right, (uint64_t)mk_leaves * 8, hipMemcpyHostToDevice, stream));
+            MerkleParams mp{d_mk_left.as<int64_t>(), d_mk_begin.as<uint32_t>(),
+                            d_mk_right.as<int64_t>(), ms.n_trees};
+            if (n_groups)
+                hipLaunchKernelGGL(k_merkle_assign, dim3((uint32_t)((n_groups + 255) / 256)),
+                                   dim3(256), 0, stream, groups.sorted,
+                                   groups.start.as<uint64_t>(), n_groups, mp,
+                                   d_group_leaf.as<int32_t>());
+            pp.group_leaf = d_group_leaf.as<int32_t>();
+        }
         DevBuf d_ov_bw, d_ov_boff, d_ov_bbits, d_ov_bk;
         std::vector<uint32_t> ov_bw_h;
         std::vector<uint64_t> ov_boff_h, ov_bbits_h;
@@ -2040,6 +2108,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 }
                 PurgeParams2 pp_src = pp_data;
                 pp_src.has_shard = 0;  // sources shadow regardless of the shard
+                pp_src.group_leaf = nullptr;  // indexed by the data groups, not these
                 launch_reconcile(groups_t, k - kd, d_srcbases, parsed, rec_t, sch_t, pp_src,
                                  d_error, stream);
             }
@@ -2104,34 +2173,10 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         if (g_validate_out) {
             // VALIDATION epilogue: per-partition repair digests instead of a
             // written sstable (k_validate_digest; Validator.rowHash)
-            bytes names;
-            std::vector<uint32_t> noff;
-            for (auto& [nm, t2] : su.js.header.regular_cols) {
-                (void)t2;
-                noff.push_back((uint32_t)names.size());
-                names.insert(names.end(), nm.begin(), nm.end());
-            }
-            for (auto& [nm, t2] : su.js.header.static_cols) {
-                (void)t2;
-                noff.push_back((uint32_t)names.size());
-                names.insert(names.end(), nm.begin(), nm.end());
-            }
-            noff.push_back((uint32_t)names.size());
-            DevBuf d_names, d_noff, d_hash;
-            d_names.alloc(names.size() + 8);
-            d_noff.alloc(noff.size() * 4);
+            ValidateNames vnames;
+            ValidateParams vpar = vnames.upload(su.js.header, sch, stream);
+            DevBuf d_hash;
             d_hash.alloc(n_groups * 32 + 32);
-            HIP_CHECK(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, stream));
-            ValidateParams vpar{};
-            vpar.names = d_names.as<uint8_t>();
-            vpar.name_off = d_noff.as<uint32_t>();
-            vpar.n_reg = (uint32_t)su.js.header.regular_cols.size();
-            vpar.n_static = (uint32_t)su.js.header.static_cols.size();
-            vpar.counters = sch.counters;
-            vpar.n_cpx = sch.n_cpx;
-            vpar.n_ck = sch.n_ck;
-            vpar.ck_w = sch.ck_w;
             {
                 uint32_t blocks2 = (uint32_t)((n_groups + 255) / 256);
                 hipLaunchKernelGGL(k_validate_digest, dim3(blocks2), dim3(256), 0, stream, opb.op,
@@ -2154,6 +2199,41 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             }
             write_file(g_validate_out, outb.data(), outb.size());
             g_validate_count = cnt;
+            {
+                std::lock_guard<std::mutex> gl(res_mu);
+                res->partitions_out += cnt;
+            }
+            return;
+        }
+        if (g_merkle) {
+            // MERKLE epilogue: the same digests, XORed into their leaves on
+            // the device; only the leaves travel to the host
+            ValidateNames vnames;
+            ValidateParams vpar = vnames.upload(su.js.header, sch, stream);
+            DevBuf d_hash, d_leaves;
+            d_hash.alloc(n_groups * 32 + 32);
+            // n_leaves x 4 hash words, then n_leaves counts
+            d_leaves.alloc((uint64_t)mk_leaves * 40);
+            HIP_CHECK(hipMemsetAsync(d_leaves.p, 0, (uint64_t)mk_leaves * 40, stream));
+            unsigned long long* d_lh = d_leaves.as<unsigned long long>();
+            unsigned long long* d_lc = d_lh + (uint64_t)mk_leaves * 4;
+            if (n_groups) {
+                uint32_t blocks2 = (uint32_t)((n_groups + 255) / 256);
+                hipLaunchKernelGGL(k_validate_digest, dim3(blocks2), dim3(256), 0, stream, opb.op,
+                                   rows_for_writer->uc, n_groups, vpar, d_hash.as<uint8_t>());
+                hipLaunchKernelGGL(k_merkle_leaf_xor, dim3(blocks2), dim3(256), 0, stream,
+                                   opb.op.keep, d_group_leaf.as<int32_t>(),
+                                   d_hash.as<uint64_t>(), n_groups, d_lh, d_lc);
+            }
+            std::vector<uint64_t> h_cnt(mk_leaves);
+            HIP_CHECK(hipStreamSynchronize(stream));
+            HIP_CHECK(hipMemcpy(g_merkle->leaf_hash, d_lh, (uint64_t)mk_leaves * 32, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(h_cnt.data(), d_lc, (uint64_t)mk_leaves * 8, hipMemcpyDeviceToHost));
+            uint64_t cnt = 0;
+            for (uint32_t i = 0; i < mk_leaves; i++) cnt += h_cnt[i];
+            if (g_merkle->leaf_partitions)
+                memcpy(g_merkle->leaf_partitions, h_cnt.data(), (uint64_t)mk_leaves * 8);
+            g_merkle->n_partitions = cnt;
             {
                 std::lock_guard<std::mutex> gl(res_mu);
                 res->partitions_out += cnt;
@@ -3394,14 +3474,43 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
     });
 }
 
-extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
-                             char* error, size_t error_len) {
+// job modes neither validation entry point takes
+static bool validate_mode_rejected(const gpuc_job* job, char* error, size_t error_len) {
     if (job->n_output_shards > 1 || job->max_output_bytes || job->n_tomb_sources > 0 ||
         job->n_keep_ranges > 0) {
         set_err(error, error_len,
                 "validation: sharding/size-split/tomb-source/keep-range modes unsupported");
+        return true;
+    }
+    return false;
+}
+
+extern "C" int gpuc_validate_merkle(const gpuc_job* job, const gpuc_merkle_spec* spec,
+                                    uint8_t* leaf_hash, uint64_t* leaf_partitions,
+                                    uint64_t* n_partitions, char* error, size_t error_len) {
+    // argument checks first: no device is probed and no input byte read
+    if (validate_mode_rejected(job, error, error_len)) return GPUC_ERR_UNSUPPORTED;
+    std::string bad = merkle_spec_error(spec);
+    if (bad.empty() && !leaf_hash) bad = "merkle: leaf_hash is NULL";
+    if (!bad.empty()) {
+        set_err(error, error_len, bad);
         return GPUC_ERR_UNSUPPORTED;
     }
+    gpuc_result res{};
+    MerkleRun run{spec, leaf_hash, leaf_partitions, 0};
+    gpuc_job vjob = *job;
+    if (!vjob.output_base) vjob.output_base = "/unused";  // nothing is written
+    g_merkle = &run;
+    int rc = gpuc_compact(&vjob, &res);
+    g_merkle = nullptr;
+    if (rc == GPUC_OK && n_partitions) *n_partitions = run.n_partitions;
+    if (rc != GPUC_OK) set_err(error, error_len, res.error);
+    return rc;
+}
+
+extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
+                             char* error, size_t error_len) {
+    if (validate_mode_rejected(job, error, error_len)) return GPUC_ERR_UNSUPPORTED;
     gpuc_result res{};
     g_validate_out = out_path;
     g_validate_count = 0;

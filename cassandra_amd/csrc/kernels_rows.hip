@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include "codec.h"
 #include "gpu_structs.h"
+#include "merkle_spec.h"
 
 namespace gpuc {
 
@@ -714,6 +715,84 @@ __global__ void k_validate_digest(OutParts op, UnfCols out, uint64_t n, Validate
     b.final16(hashes + g * 32 + 16);
 }
 
+// ---------------------------------------------------------------------------
+// Merkle-tree leaves of a validation compaction (gpuc_validate_merkle;
+// Validator.add -> MerkleTree.Leaf.addHash): leaf assignment before
+// reconcile, segmented XOR reduction of the digests after it.
+// ---------------------------------------------------------------------------
+struct MerkleParams {
+    const int64_t* tree_left;    // device copies of the checked gpuc_merkle_spec
+    const uint32_t* leaf_begin;
+    const int64_t* leaf_right;
+    uint32_t n_trees;
+};
+
+// One thread per group: the flat leaf index of the group's token, -1 when no
+// tree holds it. Runs on the sorted records BEFORE reconcile, which drops the
+// -1 groups (PurgeParams2::group_leaf) so that neither the merge nor the
+// digest spends anything on a partition outside the repair ranges.
+__global__ void k_merkle_assign(const MRec* recs, const uint64_t* group_start, uint64_t n_groups,
+                                MerkleParams mp, int32_t* group_leaf) {
+    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    int64_t token = (int64_t)(recs[group_start[g]].tok ^ 0x8000000000000000ULL);
+    group_leaf[g] = (int32_t)merkle_leaf_of(mp.tree_left, mp.leaf_begin, mp.leaf_right,
+                                            mp.n_trees, token);
+}
+
+// Segmented XOR reduction of the per-partition digests into their leaves.
+// Groups are token-sorted, so group_leaf is a sequence of runs of equal
+// values (a -1 run wherever partitions lie between trees); a purged group
+// sits inside its run and adds zeros. One lane per group: a wave-level
+// segmented inclusive scan (6 __shfl_up steps over the four hash words and
+// the count) leaves each run's total in the run's last lane of the wave,
+// which XORs it into the leaf: one atomic group per leaf-run per wave, so a
+// one-leaf tree costs n/64 atomic groups and a leaf per partition costs one
+// each. XOR and integer add commute: the result is the same bits every run.
+// Block size must be a multiple of 64.
+__global__ void k_merkle_leaf_xor(const uint8_t* keep, const int32_t* group_leaf,
+                                  const uint64_t* hashes, uint64_t n,
+                                  unsigned long long* leaf_hash,
+                                  unsigned long long* leaf_count) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    int32_t leaf = -1;
+    unsigned long long h0 = 0, h1 = 0, h2 = 0, h3 = 0;
+    uint32_t cnt = 0;
+    if (g < n) {
+        leaf = group_leaf[g];
+        if (leaf >= 0 && keep[g]) {
+            h0 = hashes[g * 4 + 0];
+            h1 = hashes[g * 4 + 1];
+            h2 = hashes[g * 4 + 2];
+            h3 = hashes[g * 4 + 3];
+            cnt = 1;
+        }
+    }
+    // every lane of the wave takes part in every shuffle (no early return above)
+    #pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        int32_t pl = __shfl_up(leaf, d);
+        unsigned long long p0 = __shfl_up(h0, d), p1 = __shfl_up(h1, d);
+        unsigned long long p2 = __shfl_up(h2, d), p3 = __shfl_up(h3, d);
+        uint32_t pc = __shfl_up(cnt, d);
+        // runs are contiguous: lane - d in the same run means all between are
+        if (lane >= d && pl == leaf) {
+            h0 ^= p0; h1 ^= p1; h2 ^= p2; h3 ^= p3;
+            cnt += pc;
+        }
+    }
+    int32_t next_leaf = __shfl_down(leaf, 1);
+    bool run_end = lane == 63 || next_leaf != leaf;
+    if (run_end && leaf >= 0 && cnt) {
+        atomicXor(&leaf_hash[(uint64_t)leaf * 4 + 0], h0);
+        atomicXor(&leaf_hash[(uint64_t)leaf * 4 + 1], h1);
+        atomicXor(&leaf_hash[(uint64_t)leaf * 4 + 2], h2);
+        atomicXor(&leaf_hash[(uint64_t)leaf * 4 + 3], h3);
+        atomicAdd(&leaf_count[leaf], (unsigned long long)cnt);
+    }
+}
+
 // total present-cell value bytes (counter arena sizing)
 __global__ void k_sum_vallen(UnfCols in, uint64_t n_cells, unsigned long long* out) {
     __shared__ unsigned long long sh;
@@ -781,6 +860,10 @@ struct PurgeParams2 {
     const int64_t* kr_hi;
     int32_t n_keep_ranges;
     int32_t invert_ranges;
+    // gpuc_validate_merkle: per-group leaf index from k_merkle_assign (indexed
+    // like the groups being reconciled); a group with -1 lies in no tree and
+    // is dropped like one outside the shard. NULL for every other caller.
+    const int32_t* group_leaf;
 };
 
 __device__ inline bool token_kept(const PurgeParams2& pp, int64_t token) {
@@ -926,7 +1009,10 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
     op.klen[g] = r0.klen;
     op.row_base[g] = out_base[g];
     op.row_count[g] = 0;
-    if (!token_kept(pp, token)) { op.keep[g] = 0; return; }
+    if (!token_kept(pp, token) || (pp.group_leaf && pp.group_leaf[g] < 0)) {
+        op.keep[g] = 0;
+        return;
+    }
     if (pp.ov_has_bloom) {
         uint64_t h[2];
         murmur3_128((const uint8_t*)op.key_addr[g], r0.klen, 0, h);

@@ -245,10 +245,52 @@ int gpuc_generate(const gpuc_gen_spec* spec, const char* dir, char* error, size_
  * (Murmur3 token, int64 BE) + 32-byte concat(murmur3_128(1000),
  * murmur3_128(2000)) hash (db/Digest.java:53-59) — to out_path instead of
  * an output sstable. The host feeds these to its MerkleTree
- * (Validator.add). Uses the same gpuc_job fields (now/gcBefore/overlaps);
+ * (Validator.add) itself; a repair over ranges, which wants the trees' leaf
+ * hashes and not one record per partition, calls gpuc_validate_merkle below.
+ * Uses the same gpuc_job fields (now/gcBefore/overlaps/has_token_range);
  * sharding/size-split/tombstone-source/keep-range modes are rejected. */
 int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
                   char* error, size_t error_len);
+
+/* VALIDATION compaction reduced to Merkle-tree leaves ON THE DEVICE
+ * (Validator.add -> MerkleTree.Leaf.addHash): the same merge + purge + digest
+ * as gpuc_validate, then every kept partition's 32-byte digest is XORed into
+ * the leaf that holds its token. The host builds its MerkleTrees as it does
+ * today (Validator.prepare / MerkleTree.init, its own midpoint arithmetic) and
+ * passes only the leaf bounds; the library never splits a range. Wrapping
+ * ranges are unwrapped by the host (Range.unwrap).
+ *
+ * Leaf i of tree t covers (prev, leaf_right[i]]: prev is tree_left[t] for the
+ * tree's first leaf, leaf_right[i-1] otherwise; compares are signed 64-bit.
+ * leaf_hash[i] is the XOR of the digests (the bytes gpuc_validate writes) of
+ * the kept output partitions whose token lies in leaf i — equal tokens with
+ * different keys share a leaf; a leaf without a partition is 32 zero bytes,
+ * count 0. A partition in no tree is not validated: not digested, not counted
+ * in *n_partitions. Purged partitions contribute nothing. has_token_range
+ * intersects with the trees. The "XOR into the leaf, zeros when empty,
+ * inner node = XOR of children" rule is the 4.0+ MerkleTree's as recalled;
+ * Validator's sizeOfRange (logging only) is not produced.
+ *
+ * GPUC_ERR_UNSUPPORTED, with the tree or leaf index in the message and before
+ * any device is probed or input byte read: a NULL spec or array; n_trees 0;
+ * leaf_begin[0] != 0 or leaf_begin not strictly increasing (a tree has at
+ * least one leaf); a tree's first leaf_right not above its tree_left;
+ * leaf_right not strictly ascending within a tree; tree_left[t+1] below tree
+ * t's last leaf_right; more than 2^31 - 1 leaves. Job modes are accepted and
+ * rejected exactly as by gpuc_validate. */
+typedef struct gpuc_merkle_spec {
+    uint32_t n_trees;            /* repair ranges == MerkleTrees, ascending, disjoint */
+    const int64_t* tree_left;    /* n_trees: EXCLUSIVE left token of each tree's range */
+    const uint32_t* leaf_begin;  /* n_trees + 1 offsets into leaf_right; leaf_begin[0] == 0 */
+    const int64_t* leaf_right;   /* INCLUSIVE right token of each leaf, in tree order;
+                                    a tree's last entry is the right end of its range */
+} gpuc_merkle_spec;
+
+int gpuc_validate_merkle(const gpuc_job* job, const gpuc_merkle_spec* spec,
+                         uint8_t* leaf_hash,         /* n_leaves * 32 bytes, out */
+                         uint64_t* leaf_partitions,  /* n_leaves, out; may be NULL */
+                         uint64_t* n_partitions,     /* partitions validated; may be NULL */
+                         char* error, size_t error_len);
 
 /* Memtable flush (the write-path seed): n unsorted UNIQUE-key rows ->
  * token-sorted on device -> one complete `oa` sstable under output_base.
