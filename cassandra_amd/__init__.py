@@ -189,6 +189,11 @@ def load_library(path=None):
             ctypes.POINTER(GpucJob), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
             ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
         lib.gpuc_validate_merkle.restype = ctypes.c_int
+    if hasattr(lib, "gpuc_compact_routed"):  # absent in frozen A/B probe builds
+        lib.gpuc_compact_routed.argtypes = [
+            ctypes.POINTER(GpucJob), ctypes.c_void_p, ctypes.POINTER(GpucResult),
+            ctypes.c_void_p]
+        lib.gpuc_compact_routed.restype = ctypes.c_int
     lib.gpuc_version.restype = ctypes.c_char_p
     lib.gpuc_device_count.restype = ctypes.c_int
     _lib = lib
@@ -654,6 +659,115 @@ def device_count():
     return load_library().gpuc_device_count()
 
 
+def _make_job(
+    input_bases,
+    output_base,
+    now_sec=1800000000,
+    gc_before=INT64_MIN,
+    never_purge=False,
+    enforce_strict_liveness=False,
+    overlaps=None,
+    token_range=None,
+    device=0,
+    n_output_shards=1,
+    cancel_flag=None,
+    tombstone_sources=None,
+    cell_level_gc=False,
+    keep_ranges=None,
+    invert_ranges=False,
+    output_chunk_length=0,
+    max_output_bytes=0,
+):
+    """The gpuc_job of compact() / compact_routed() (same keywords)."""
+    job = GpucJob()
+    keep_alive = []  # buffers the job points into; the caller holds them for the call
+    arr = (ctypes.c_char_p * len(input_bases))(*[b.encode() for b in input_bases])
+    job.input_bases = arr
+    job.n_inputs = len(input_bases)
+    job.output_base = output_base.encode() if output_base is not None else None
+    job.now_sec = now_sec
+    job.gc_before = gc_before
+    job.never_purge = 1 if never_purge else 0
+    job.enforce_strict_liveness = 1 if enforce_strict_liveness else 0
+    if overlaps:
+        ovr = (GpucPurgeRange * len(overlaps))()
+        for i, ov in enumerate(overlaps):
+            if len(ov) == 3:
+                lo, hi, ts = ov
+                blm = None
+            else:
+                # (lo, hi, ts, filter_db_path): load the sstable's Filter.db
+                # for the per-key bloom-checked evaluator
+                lo, hi, ts, fpath = ov
+                raw = open(fpath, "rb").read()
+                k = int.from_bytes(raw[0:4], "big")
+                words = int.from_bytes(raw[4:8], "big")
+                bits = raw[8:8 + words * 8]
+                buf = (ctypes.c_uint32 * (len(bits) // 4)).from_buffer_copy(bits)
+                keep_alive.append(buf)
+                blm = (buf, words * 64, k)
+            ovr[i].token_lo, ovr[i].token_hi, ovr[i].min_timestamp = lo, hi, ts
+            if blm is not None:
+                ovr[i].bloom_bits = ctypes.cast(blm[0], ctypes.POINTER(ctypes.c_uint32))
+                ovr[i].bloom_bit_len = blm[1]
+                ovr[i].bloom_hash_count = blm[2]
+        job.overlaps = ovr
+        job.n_overlaps = len(overlaps)
+    if token_range is not None:
+        job.has_token_range = 1
+        job.token_lo, job.token_hi = token_range
+    if keep_ranges:
+        kr = (GpucPurgeRange * len(keep_ranges))()
+        for i, (lo, hi) in enumerate(keep_ranges):
+            kr[i].token_lo, kr[i].token_hi = lo, hi
+        job.keep_ranges = kr
+        job.n_keep_ranges = len(keep_ranges)
+        job.invert_ranges = 1 if invert_ranges else 0
+    job.device = device
+    job.n_output_shards = n_output_shards
+    if cancel_flag is not None:
+        if isinstance(cancel_flag, ctypes.c_int32):
+            cancel_flag = ctypes.pointer(cancel_flag)
+        job.cancel_flag = ctypes.cast(cancel_flag, ctypes.POINTER(ctypes.c_int32))
+    if tombstone_sources:
+        tarr = (ctypes.c_char_p * len(tombstone_sources))(*[b.encode() for b in tombstone_sources])
+        job.tombstone_source_bases = tarr
+        job.n_tomb_sources = len(tombstone_sources)
+    job.cell_level_gc = 1 if cell_level_gc else 0
+    job.output_chunk_length = output_chunk_length
+    job.max_output_bytes = max_output_bytes
+    return job, keep_alive
+
+
+def _result_dict(res):
+    return {
+        "input_uncompressed_bytes": res.input_uncompressed_bytes,
+        "output_uncompressed_bytes": res.output_uncompressed_bytes,
+        "output_compressed_bytes": res.output_compressed_bytes,
+        "partitions_in": res.partitions_in,
+        "partitions_out": res.partitions_out,
+        "rows_in": res.rows_in,
+        "rows_out": res.rows_out,
+        "n_outputs": res.n_outputs,
+        "merged_counts": list(res.merged_counts),
+        "ms": {
+            "read_io": res.ms_read_io,
+            "h2d": res.ms_h2d,
+            "decompress": res.ms_decompress,
+            "parse": res.ms_parse,
+            "merge": res.ms_merge,
+            "reconcile": res.ms_reconcile,
+            "serialize": res.ms_serialize,
+            "compress": res.ms_compress,
+            "d2h": res.ms_d2h,
+            "write_io": res.ms_write_io,
+            "total": res.ms_total,
+        },
+        "dominant_kernel": res.dominant_kernel.decode(),
+        "dominant_kernel_ms": res.dominant_kernel_ms,
+    }
+
+
 def compact(
     input_bases,
     output_base,
@@ -687,93 +801,126 @@ def compact(
       +2, ...; the result's "n_outputs" says how many were written.
     """
     lib = load_library()
-    job = GpucJob()
-    arr = (ctypes.c_char_p * len(input_bases))(*[b.encode() for b in input_bases])
-    job.input_bases = arr
-    job.n_inputs = len(input_bases)
-    job.output_base = output_base.encode()
-    job.now_sec = now_sec
-    job.gc_before = gc_before
-    job.never_purge = 1 if never_purge else 0
-    job.enforce_strict_liveness = 1 if enforce_strict_liveness else 0
-    if overlaps:
-        ovr = (GpucPurgeRange * len(overlaps))()
-        _bloom_keep = []  # keep the bit buffers alive for the call
-        for i, ov in enumerate(overlaps):
-            if len(ov) == 3:
-                lo, hi, ts = ov
-                blm = None
-            else:
-                # (lo, hi, ts, filter_db_path): load the sstable's Filter.db
-                # for the per-key bloom-checked evaluator
-                lo, hi, ts, fpath = ov
-                raw = open(fpath, "rb").read()
-                k = int.from_bytes(raw[0:4], "big")
-                words = int.from_bytes(raw[4:8], "big")
-                bits = raw[8:8 + words * 8]
-                buf = (ctypes.c_uint32 * (len(bits) // 4)).from_buffer_copy(bits)
-                _bloom_keep.append(buf)
-                blm = (buf, words * 64, k)
-            ovr[i].token_lo, ovr[i].token_hi, ovr[i].min_timestamp = lo, hi, ts
-            if blm is not None:
-                ovr[i].bloom_bits = ctypes.cast(blm[0], ctypes.POINTER(ctypes.c_uint32))
-                ovr[i].bloom_bit_len = blm[1]
-                ovr[i].bloom_hash_count = blm[2]
-        job.overlaps = ovr
-        job.n_overlaps = len(overlaps)
-    if token_range is not None:
-        job.has_token_range = 1
-        job.token_lo, job.token_hi = token_range
-    if keep_ranges:
-        kr = (GpucPurgeRange * len(keep_ranges))()
-        for i, (lo, hi) in enumerate(keep_ranges):
-            kr[i].token_lo, kr[i].token_hi = lo, hi
-        job.keep_ranges = kr
-        job.n_keep_ranges = len(keep_ranges)
-        job.invert_ranges = 1 if invert_ranges else 0
-    job.device = device
-    job.n_output_shards = n_output_shards
-    if cancel_flag is not None:
-        if isinstance(cancel_flag, ctypes.c_int32):
-            cancel_flag = ctypes.pointer(cancel_flag)
-        job.cancel_flag = ctypes.cast(cancel_flag, ctypes.POINTER(ctypes.c_int32))
-    if tombstone_sources:
-        tarr = (ctypes.c_char_p * len(tombstone_sources))(*[b.encode() for b in tombstone_sources])
-        job.tombstone_source_bases = tarr
-        job.n_tomb_sources = len(tombstone_sources)
-    job.cell_level_gc = 1 if cell_level_gc else 0
-    job.output_chunk_length = output_chunk_length
-    job.max_output_bytes = max_output_bytes
+    job, _keep_alive = _make_job(
+        input_bases, output_base, now_sec=now_sec, gc_before=gc_before, never_purge=never_purge,
+        enforce_strict_liveness=enforce_strict_liveness, overlaps=overlaps,
+        token_range=token_range, device=device, n_output_shards=n_output_shards,
+        cancel_flag=cancel_flag, tombstone_sources=tombstone_sources,
+        cell_level_gc=cell_level_gc, keep_ranges=keep_ranges, invert_ranges=invert_ranges,
+        output_chunk_length=output_chunk_length, max_output_bytes=max_output_bytes)
     res = GpucResult()
     rc = lib.gpuc_compact(ctypes.byref(job), ctypes.byref(res))
     if rc != 0:
         raise GpuCompactError(f"gpuc_compact rc={rc}: {res.error.decode(errors='replace')}")
-    return {
-        "input_uncompressed_bytes": res.input_uncompressed_bytes,
-        "output_uncompressed_bytes": res.output_uncompressed_bytes,
-        "output_compressed_bytes": res.output_compressed_bytes,
-        "partitions_in": res.partitions_in,
-        "partitions_out": res.partitions_out,
-        "rows_in": res.rows_in,
-        "rows_out": res.rows_out,
-        "n_outputs": res.n_outputs,
-        "merged_counts": list(res.merged_counts),
-        "ms": {
-            "read_io": res.ms_read_io,
-            "h2d": res.ms_h2d,
-            "decompress": res.ms_decompress,
-            "parse": res.ms_parse,
-            "merge": res.ms_merge,
-            "reconcile": res.ms_reconcile,
-            "serialize": res.ms_serialize,
-            "compress": res.ms_compress,
-            "d2h": res.ms_d2h,
-            "write_io": res.ms_write_io,
-            "total": res.ms_total,
-        },
-        "dominant_kernel": res.dominant_kernel.decode(),
-        "dominant_kernel_ms": res.dominant_kernel_ms,
-    }
+    return _result_dict(res)
+
+
+class GpucRouteSpec(ctypes.Structure):
+    _fields_ = [
+        ("n_outputs", ctypes.c_uint32),
+        ("output_bases", ctypes.POINTER(ctypes.c_char_p)),
+        ("n_ranges", ctypes.c_uint32),
+        ("range_lo", ctypes.POINTER(ctypes.c_int64)),
+        ("range_hi", ctypes.POINTER(ctypes.c_int64)),
+        ("range_output", ctypes.POINTER(ctypes.c_int32)),
+        ("default_output", ctypes.c_int32),
+    ]
+
+
+class GpucRouteOutput(ctypes.Structure):
+    _fields_ = [
+        ("written", ctypes.c_uint32),
+        ("partitions", ctypes.c_uint64),
+        ("rows", ctypes.c_uint64),
+        ("uncompressed_bytes", ctypes.c_uint64),
+        ("compressed_bytes", ctypes.c_uint64),
+    ]
+
+
+def compact_routed(input_bases, output_bases, ranges, default_output, raw_spec=None,
+                   want_outputs=True, **job_kw):
+    """One compaction routed into several sstables by token range
+    (gpuc_compact_routed): merge, reconcile and purge once, then one output
+    per class of partitions.
+
+    output_bases: one path prefix per output.
+    ranges: list of (lo, hi, output), both bounds inclusive, ascending and
+      disjoint; output is an index into output_bases, or -1 to drop.
+    default_output: where tokens in no range go, or -1 to drop them.
+    job_kw: the keywords of compact() (output_base excluded).
+    Returns compact()'s dict plus "outputs": one dict per output with
+    "written", "partitions", "rows", "uncompressed_bytes", "compressed_bytes";
+    an output nothing was routed to has written == 0 and no file.
+
+    raw_spec: escape hatch that skips the four arguments above: (n_outputs,
+      output_bases, n_ranges, range_lo, range_hi, range_output,
+      default_output), the four arrays as lists or None (== NULL; a None
+      inside output_bases is a NULL base), handed to the library UNCHECKED
+      (nothing here validates a spec: refusing a bad one is the library's
+      job). raw_spec="null" passes a NULL spec.
+    """
+    lib = load_library()
+    job, _keep_alive = _make_job(input_bases, None, **job_kw)
+    spec_ref = None
+    n_out = 0
+    if raw_spec != "null":
+        if raw_spec is None:
+            raw_spec = (len(output_bases), list(output_bases), len(ranges),
+                        [r[0] for r in ranges], [r[1] for r in ranges],
+                        [r[2] for r in ranges], default_output)
+        n_out, bases, n_ranges, los, his, outs, dflt = raw_spec
+        spec = GpucRouteSpec()
+        spec.n_outputs = n_out
+        spec.n_ranges = n_ranges
+        spec.default_output = dflt
+        if bases is not None:
+            barr = (ctypes.c_char_p * max(len(bases), 1))(
+                *[b.encode() if b is not None else None for b in bases])
+            _keep_alive.append(barr)
+            spec.output_bases = barr
+        for field, ctype, vals in (("range_lo", ctypes.c_int64, los),
+                                   ("range_hi", ctypes.c_int64, his),
+                                   ("range_output", ctypes.c_int32, outs)):
+            if vals is None:
+                continue  # stays NULL
+            buf = (ctype * max(len(vals), 1))(*vals)
+            _keep_alive.append(buf)
+            setattr(spec, field, ctypes.cast(buf, ctypes.POINTER(ctype)))
+        spec_ref = ctypes.byref(spec)
+    outs_arr = None
+    if want_outputs and 0 < n_out <= 1024:
+        outs_arr = (GpucRouteOutput * n_out)()
+    res = GpucResult()
+    rc = lib.gpuc_compact_routed(ctypes.byref(job), spec_ref, ctypes.byref(res), outs_arr)
+    if rc != 0:
+        raise GpuCompactError(
+            f"gpuc_compact_routed rc={rc}: {res.error.decode(errors='replace')}")
+    d = _result_dict(res)
+    d["outputs"] = [
+        {"written": o.written, "partitions": o.partitions, "rows": o.rows,
+         "uncompressed_bytes": o.uncompressed_bytes, "compressed_bytes": o.compressed_bytes}
+        for o in (outs_arr or [])]
+    return d
+
+
+def anticompact(input_bases, full_base, transient_base, unrepaired_base, full_ranges,
+                transient_ranges=(), **job_kw):
+    """One anticompaction (CompactionManager.antiCompactGroup) in one call:
+    partitions in full_ranges go to full_base (output 0), those in
+    transient_ranges to transient_base (output 1), the rest to unrepaired_base
+    (output 2). Ranges are (lo, hi) with both bounds inclusive. Raises
+    ValueError when a full and a transient range overlap. Runs with
+    never_purge, as the reference's NO_GC controller purges nothing during an
+    anticompaction. Returns compact_routed()'s dict."""
+    rs = sorted([(lo, hi, 0) for lo, hi in full_ranges] +
+                [(lo, hi, 1) for lo, hi in transient_ranges])
+    for a, b in zip(rs, rs[1:]):
+        if a[1] >= b[0] and a[2] != b[2]:
+            raise ValueError(
+                f"full and transient ranges overlap: [{a[0]}, {a[1]}] and [{b[0]}, {b[1]}]")
+    job_kw["never_purge"] = True
+    return compact_routed(input_bases, [full_base, transient_base, unrepaired_base], rs, 2,
+                          **job_kw)
 
 
 def validate(input_bases, out_path, now_sec=1800000000, gc_before=INT64_MIN,

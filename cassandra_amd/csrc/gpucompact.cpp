@@ -72,6 +72,13 @@ struct MerkleRun {
     uint64_t n_partitions;      // out: sum of the leaf counts
 };
 static thread_local MerkleRun* g_merkle = nullptr;
+// Routed outputs: set by gpuc_compact_routed around its run. The spec is
+// checked before it gets here.
+struct RouteRun {
+    const gpuc_route_spec* spec;
+    gpuc_route_output* outputs;  // n_outputs, out; may be NULL
+};
+static thread_local RouteRun* g_route = nullptr;
 static double g_trace_t0 = 0;
 static double trace_wall() {
     struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -837,7 +844,7 @@ struct OutputImage {
 // stages 3 and 4 of the writer: slab drain of the compressed chunks into
 // Data.db on `cstream`, then the component tail. Returns with both streams
 // idle and every component of opt.base written.
-static void drain_and_finish(const OutputImage& im, const OutPartsBuf& opb, const SerParams2& sp,
+static void drain_and_finish(const OutputImage& im, const OutParts& op, const SerParams2& sp,
                              const DevBuf& d_tomb, uint32_t tomb_cap, const TableTypes& types,
                              const OutputOptions& opt, hipStream_t stream, hipStream_t cstream,
                              hipEvent_t ev2, hipEvent_t ev4, WriteDeviceOut& w) {
@@ -977,14 +984,14 @@ static void drain_and_finish(const OutputImage& im, const OutPartsBuf& opb, cons
             d_kh.alloc(n_groups * 8 + 8);
             uint32_t blocks = (uint32_t)((n_groups + 255) / 256);
             if (n_groups)
-                hipLaunchKernelGGL(k_key_hash2, dim3(blocks), dim3(256), 0, stream, opb.op,
+                hipLaunchKernelGGL(k_key_hash2, dim3(blocks), dim3(256), 0, stream, op,
                                    im.g1, d_kh.as<uint64_t>(), im.g0);
             std::vector<uint64_t> kh(n_groups);
             std::vector<uint8_t> keep(n_groups);
             if (n_groups) {
                 HIP_CHECK(hipStreamSynchronize(stream));
                 HIP_CHECK(hipMemcpy(kh.data(), d_kh.p, n_groups * 8, hipMemcpyDeviceToHost));
-                HIP_CHECK(hipMemcpy(keep.data(), opb.op.keep + im.g0, n_groups, hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(keep.data(), op.keep + im.g0, n_groups, hipMemcpyDeviceToHost));
             }
             m.key_hashes.reserve(n_groups);
             for (uint64_t g2 = 0; g2 < n_groups; g2++)
@@ -999,8 +1006,8 @@ static void drain_and_finish(const OutputImage& im, const OutPartsBuf& opb, cons
                 uint64_t g = which ? lg : fg;
                 uint64_t ka;
                 uint16_t kl;
-                HIP_CHECK(hipMemcpy(&ka, opb.op.key_addr + g, 8, hipMemcpyDeviceToHost));
-                HIP_CHECK(hipMemcpy(&kl, opb.op.klen + g, 2, hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(&ka, op.key_addr + g, 8, hipMemcpyDeviceToHost));
+                HIP_CHECK(hipMemcpy(&kl, op.klen + g, 2, hipMemcpyDeviceToHost));
                 bytes kb(kl);
                 HIP_CHECK(hipMemcpy(kb.data(), (const void*)ka, kl, hipMemcpyDeviceToHost));
                 (which ? m.last_key : m.first_key) = kb;
@@ -1039,7 +1046,7 @@ static void drain_and_finish(const OutputImage& im, const OutPartsBuf& opb, cons
     }
 }
 
-static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfColsBuf& rows,
+static WriteDeviceOut write_sstable_device(const OutParts& op, const UnfColsBuf& rows,
                                            uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
                                            DevBuf& d_tomb, uint32_t tomb_cap,
                                            const TableTypes& types, const OutputOptions& opt,
@@ -1070,7 +1077,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     // ---- collect stats (needed before bloom sizing) ----
     {
         uint64_t blocks = (n_groups + 255) / 256;
-        hipLaunchKernelGGL(k_collect_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, opb.op,
+        hipLaunchKernelGGL(k_collect_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, op,
                            rows.uc, n_groups, sp.sch.n_cols, sp.sch.n_cpx, d_stats.as<OutStats>(),
                            d_tomb.as<uint32_t>(), tomb_cap);
     }
@@ -1084,7 +1091,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     d_infsz.alloc(n_groups * 8);
     {
         uint64_t blocks = (n_groups + 255) / 256;
-        hipLaunchKernelGGL(k_sizes_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, opb.op,
+        hipLaunchKernelGGL(k_sizes_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, op,
                            rows.uc, n_groups, sp, d_psize.as<uint64_t>(), d_isize.as<uint64_t>(),
                            d_nblocks.as<uint32_t>(), d_infsz.as<uint64_t>(),
                            d_stats.as<OutStats>(), d_ps_off.as<int64_t>(), (int32_t)ps_off_h.size(),
@@ -1094,7 +1101,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     {
         uint64_t blocks = (n_groups + 255) / 256;
         hipLaunchKernelGGL(k_index_sizes_rows, dim3((uint32_t)blocks), dim3(256), 0, stream,
-                           opb.op, n_groups, sp, d_psize.as<uint64_t>(), d_nblocks.as<uint32_t>(),
+                           op, n_groups, sp, d_psize.as<uint64_t>(), d_nblocks.as<uint32_t>(),
                            d_infsz.as<uint64_t>(), d_isize.as<uint64_t>());
     }
     uint64_t total_idx = exscan_u64(d_isize.as<uint64_t>(), n_groups, stream);
@@ -1150,7 +1157,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
         uint64_t blocks = (std::max<uint64_t>(ge - gs, 1) + waves_per_block - 1) / waves_per_block;
         if (ge > gs)
             hipLaunchKernelGGL(k_serialize_rows, dim3((uint32_t)blocks),
-                               dim3(WAVE * waves_per_block), 0, stream, opb.op, rows.uc, ge,
+                               dim3(WAVE * waves_per_block), 0, stream, op, rows.uc, ge,
                                sp, d_psize.as<uint64_t>(), d_isize.as<uint64_t>(),
                                d_nblocks.as<uint32_t>(), d_infsz.as<uint64_t>(),
                                d_out_data.as<uint8_t>(), d_out_index.as<uint8_t>(),
@@ -1235,7 +1242,7 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     im.hst = hst;
     im.ev_c = &ev_c;
     im.index_late = NSEG > 1;
-    drain_and_finish(im, opb, sp, d_tomb, tomb_cap, types, opt, stream, cstream, ev2, ev4, w);
+    drain_and_finish(im, op, sp, d_tomb, tomb_cap, types, opt, stream, cstream, ev2, ev4, w);
     w.uncompressed_len = total_unc;
     float t01, t12, t23;
     HIP_CHECK(hipEventElapsedTime(&t01, ev0, ev1));
@@ -1245,6 +1252,17 @@ static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfCols
     w.ms_serialize = t12;
     w.ms_compress = t23;
     return w;
+}
+
+// the writer reads only the OutParts view; a routed output passes a view whose
+// keep points at that output's mask, everyone else their buffer's own
+static WriteDeviceOut write_sstable_device(const OutPartsBuf& opb, const UnfColsBuf& rows,
+                                           uint64_t n_groups, SerParams2 sp, DevBuf& d_stats,
+                                           DevBuf& d_tomb, uint32_t tomb_cap,
+                                           const TableTypes& types, const OutputOptions& opt,
+                                           hipStream_t stream) {
+    return write_sstable_device(opb.op, rows, n_groups, sp, d_stats, d_tomb, tomb_cap, types, opt,
+                                stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1552,7 +1570,7 @@ static WriteDeviceOut write_sstables_size_split(const OutPartsBuf& opb, const Un
         OutputOptions opt_k = opt;
         opt_k.base = output_base_plus(opt.base, tot.n_outputs);
         WriteDeviceOut w;
-        drain_and_finish(im, opb, sp, d_tomb, tomb_cap, types, opt_k, stream, cstream, ev2, ev4, w);
+        drain_and_finish(im, opb.op, sp, d_tomb, tomb_cap, types, opt_k, stream, cstream, ev2, ev4, w);
         if (g_trace)
             fprintf(stderr, "[split] output %u groups=[%llu,%llu) unc=%llu comp=%llu windows=%u\n",
                     tot.n_outputs, (unsigned long long)g0, (unsigned long long)g1,
@@ -2242,7 +2260,75 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         }
         const OutputOptions oopt{out_base_str, su.cinfos[0].snappy, su.bti, su.out_chunk_len, wslot};
         WriteDeviceOut w;
-        if (job->max_output_bytes) {
+        if (g_route) {
+            // ROUTED outputs: classify the kept partitions by token once, then
+            // run the writer once per output under that output's keep mask
+            const gpuc_route_spec& rs = *g_route->spec;
+            const uint32_t n_out = rs.n_outputs;
+            DevBuf d_rlo, d_rhi, d_rout, d_cls, d_mask, d_cnt, d_stats_o;
+            d_rlo.alloc((uint64_t)rs.n_ranges * 8 + 8);
+            d_rhi.alloc((uint64_t)rs.n_ranges * 8 + 8);
+            d_rout.alloc((uint64_t)rs.n_ranges * 4 + 4);
+            d_cls.alloc(n_groups + 1);
+            d_mask.alloc(n_groups + 1);
+            d_cnt.alloc((uint64_t)n_out * 8);
+            d_stats_o.alloc(sizeof(OutStats));
+            if (rs.n_ranges) {
+                HIP_CHECK(hipMemcpyAsync(d_rlo.p, rs.range_lo, (uint64_t)rs.n_ranges * 8, hipMemcpyHostToDevice, stream));
+                HIP_CHECK(hipMemcpyAsync(d_rhi.p, rs.range_hi, (uint64_t)rs.n_ranges * 8, hipMemcpyHostToDevice, stream));
+                HIP_CHECK(hipMemcpyAsync(d_rout.p, rs.range_output, (uint64_t)rs.n_ranges * 4, hipMemcpyHostToDevice, stream));
+            }
+            HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (uint64_t)n_out * 8, stream));
+            const uint32_t blocks_r = (uint32_t)((n_groups + 255) / 256);
+            if (n_groups) {
+                RouteParams rp{d_rlo.as<int64_t>(), d_rhi.as<int64_t>(), d_rout.as<int32_t>(),
+                               rs.n_ranges, rs.default_output, n_out};
+                hipLaunchKernelGGL(k_route_parts, dim3(blocks_r), dim3(256), 0, stream,
+                                   opb.op.token, opb.op.keep, n_groups, rp, d_cls.as<uint8_t>(),
+                                   d_cnt.as<unsigned long long>());
+            }
+            std::vector<uint64_t> h_cnt(n_out);
+            HIP_CHECK(hipStreamSynchronize(stream));
+            HIP_CHECK(hipMemcpy(h_cnt.data(), d_cnt.p, (uint64_t)n_out * 8, hipMemcpyDeviceToHost));
+            w.n_outputs = 0;
+            OutParts view = opb.op;
+            view.keep = d_mask.as<uint8_t>();
+            for (uint32_t o = 0; o < n_out; o++) {
+                gpuc_route_output ro{};
+                if (h_cnt[o]) {
+                    check_cancel(job);
+                    hipLaunchKernelGGL(k_route_mask, dim3(blocks_r), dim3(256), 0, stream,
+                                       d_cls.as<uint8_t>(), n_groups, (uint8_t)o,
+                                       d_mask.as<uint8_t>());
+                    init_outstats(d_stats_o, stream);
+                    OutputOptions oopt_o = oopt;
+                    oopt_o.base = rs.output_bases[o];
+                    WriteDeviceOut wo =
+                        write_sstable_device(view, *rows_for_writer, n_groups, sp2, d_stats_o,
+                                             d_tomb, tomb_cap, su.js.header, oopt_o, stream);
+                    if (wo.partitions != h_cnt[o])
+                        throw std::runtime_error("routed output " + std::to_string(o) +
+                                                 ": writer and router disagree on partitions");
+                    ro.written = 1;
+                    ro.partitions = wo.partitions;
+                    ro.rows = wo.rows;
+                    ro.uncompressed_bytes = wo.uncompressed_len;
+                    ro.compressed_bytes = wo.compressed_len;
+                    w.n_outputs++;
+                    w.partitions += wo.partitions;
+                    w.rows += wo.rows;
+                    w.cells += wo.cells;
+                    w.uncompressed_len += wo.uncompressed_len;
+                    w.compressed_len += wo.compressed_len;
+                    w.ms_sizes += wo.ms_sizes;
+                    w.ms_serialize += wo.ms_serialize;
+                    w.ms_compress += wo.ms_compress;
+                    w.ms_d2h += wo.ms_d2h;
+                    w.ms_io += wo.ms_io;
+                }
+                if (g_route->outputs) g_route->outputs[o] = ro;
+            }
+        } else if (job->max_output_bytes) {
             // r of the speculative window: the inputs' own compressed/uncompressed ratio
             uint64_t in_comp = 0, in_unc = 0;
             for (int s = 0; s < kd; s++) {
@@ -3505,6 +3591,29 @@ extern "C" int gpuc_validate_merkle(const gpuc_job* job, const gpuc_merkle_spec*
     g_merkle = nullptr;
     if (rc == GPUC_OK && n_partitions) *n_partitions = run.n_partitions;
     if (rc != GPUC_OK) set_err(error, error_len, res.error);
+    return rc;
+}
+
+extern "C" int gpuc_compact_routed(const gpuc_job* job, const gpuc_route_spec* spec,
+                                   gpuc_result* res, gpuc_route_output* outputs) {
+    // argument checks first: no device is probed and no input byte read
+    std::string bad;
+    if (job->n_keep_ranges > 0) bad = "routed outputs: keep_ranges unsupported (route by the spec)";
+    else if (job->n_output_shards > 1) bad = "routed outputs: n_output_shards unsupported";
+    else if (job->max_output_bytes) bad = "routed outputs: max_output_bytes unsupported";
+    else bad = route_spec_error(spec);
+    if (!bad.empty()) {
+        memset(res, 0, sizeof(*res));
+        set_err(res->error, sizeof(res->error), bad);
+        return GPUC_ERR_UNSUPPORTED;
+    }
+    if (outputs) memset(outputs, 0, sizeof(*outputs) * spec->n_outputs);
+    RouteRun run{spec, outputs};
+    gpuc_job rjob = *job;
+    rjob.output_base = spec->output_bases[0];  // unused: every output has its own base
+    g_route = &run;
+    int rc = gpuc_compact(&rjob, res);
+    g_route = nullptr;
     return rc;
 }
 

@@ -17,6 +17,7 @@
 #include "codec.h"
 #include "gpu_structs.h"
 #include "merkle_spec.h"
+#include "route_spec.h"
 
 namespace gpuc {
 
@@ -791,6 +792,55 @@ __global__ void k_merkle_leaf_xor(const uint8_t* keep, const int32_t* group_leaf
         atomicXor(&leaf_hash[(uint64_t)leaf * 4 + 3], h3);
         atomicAdd(&leaf_count[leaf], (unsigned long long)cnt);
     }
+}
+
+// ---------------------------------------------------------------------------
+// routed outputs (gpuc_compact_routed; CompactionManager.antiCompactGroup):
+// classify every kept partition by token, then hand the writer one keep mask
+// per output.
+// ---------------------------------------------------------------------------
+struct RouteParams {
+    const int64_t* lo;    // device copies of the checked gpuc_route_spec
+    const int64_t* hi;
+    const int32_t* out;
+    uint32_t n_ranges;
+    int32_t default_output;
+    uint32_t n_outputs;   // <= ROUTE_MAX_OUTPUTS
+};
+
+constexpr uint8_t ROUTE_NONE = 0xFF;  // class of a group no output receives
+
+// One thread per group: the group's output (class) byte, ROUTE_NONE for a
+// group that is not kept or whose token is dropped, and the kept partitions
+// per class. Counts are reduced in LDS first, then one global atomic per
+// block and class present (as k_merged_hist does).
+__global__ void k_route_parts(const int64_t* token, const uint8_t* keep, uint64_t n,
+                              RouteParams rp, uint8_t* cls, unsigned long long* counts) {
+    __shared__ unsigned int sh[ROUTE_MAX_OUTPUTS];
+    for (uint32_t i = threadIdx.x; i < ROUTE_MAX_OUTPUTS; i += blockDim.x) sh[i] = 0;
+    __syncthreads();
+    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n) {
+        int32_t o = -1;
+        if (keep[g])
+            o = route_output_of(rp.lo, rp.hi, rp.out, rp.n_ranges, rp.default_output, token[g]);
+        // a checked spec keeps o below n_outputs; the test keeps a bad one inside sh[]
+        if (o >= 0 && (uint32_t)o < rp.n_outputs) {
+            cls[g] = (uint8_t)o;
+            atomicAdd(&sh[o], 1u);
+        } else {
+            cls[g] = ROUTE_NONE;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < rp.n_outputs; i += blockDim.x)
+        if (sh[i]) atomicAdd(&counts[i], (unsigned long long)sh[i]);
+}
+
+// keep mask of output c, into one buffer reused for every output
+__global__ void k_route_mask(const uint8_t* cls, uint64_t n, uint8_t c, uint8_t* keep_c) {
+    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n) keep_c[g] = cls[g] == c ? 1 : 0;
 }
 
 // total present-cell value bytes (counter arena sizing)

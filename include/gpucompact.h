@@ -111,7 +111,9 @@ typedef struct gpuc_job {
     /* anticompaction split (CompactionManager.antiCompactGroup / RepairFinishedCompactionTask):
        keep only partitions whose token falls in one of these inclusive ranges
        (invert_ranges=1 keeps the complement). One anticompaction = two calls:
-       ranges -> the repaired output, ranges+invert -> the unrepaired one. */
+       ranges -> the repaired output, ranges+invert -> the unrepaired one.
+       gpuc_compact_routed below writes all outputs of an anticompaction
+       (three with transient replication) from ONE pass over the inputs. */
     const gpuc_purge_range* keep_ranges;  /* min_timestamp field unused */
     int32_t n_keep_ranges;
     int32_t invert_ranges;
@@ -193,6 +195,67 @@ typedef struct gpuc_result {
 
 /* One compaction task. Returns GPUC_OK or an error code (message in result->error). */
 int gpuc_compact(const gpuc_job* job, gpuc_result* result);
+
+/* One compaction routed into several sstables by token range
+ * (CompactionManager.antiCompactGroup: one merge, a fully-repaired, a
+ * transiently-repaired and an unrepaired writer chosen per partition by the
+ * ranges its token falls in; CompactionAwareWriter.maybeSwitchWriter switching
+ * data directories at disk-boundary tokens has the same shape). Merge,
+ * reconcile, garbage-skip and purge run exactly as gpuc_compact runs them for
+ * the job, ONCE; every surviving partition is then classified on the device
+ * and the writer back end runs once per output.
+ *
+ * A token t goes to range_output[i] of the range with range_lo[i] <= t <=
+ * range_hi[i] (both bounds inclusive, signed compares), else to
+ * default_output; -1 drops the partition. Adjacent ranges may name the same
+ * output and several ranges may share one; equal tokens with different keys
+ * land together. Output o is byte-identical, in all component files, to what
+ * gpuc_compact writes for the same job with keep_ranges == the ranges routed
+ * to o (the default output: all ranges with invert_ranges). The serialization
+ * header (SerializationHeader.make stats, the column union) comes from the
+ * inputs and is the same for every output; statistics, bloom filter, Summary,
+ * first/last key, histograms and the tombstone list are each output's own.
+ *
+ * An output that receives no kept partition creates NO file and reports
+ * written == 0 — the reference's SSTableRewriter aborts a writer nothing was
+ * appended to (recalled, not checked against the Java sources). This differs
+ * on purpose from gpuc_compact, which writes one empty sstable when nothing is
+ * kept.
+ *
+ * result: n_outputs is the number of outputs written; partitions_out,
+ * rows_out, the byte counts and the ms_* writer phases are sums over the
+ * outputs; partitions_in, rows_in and merged_counts are job-wide.
+ * cancel_flag is also polled between outputs. job->output_base is ignored
+ * and may be NULL. Accepted with has_token_range, overlaps (blooms included),
+ * gc_before / never_purge, tombstone sources, output_chunk_length, Snappy,
+ * `da` inputs and inputs with different headers.
+ *
+ * GPUC_ERR_UNSUPPORTED (message in result->error, naming the offending index
+ * where one applies) before any device is probed or input byte read: a NULL
+ * spec, or a NULL array with a non-zero count; n_outputs 0 or above 32; a
+ * NULL or empty output base, or two equal ones; range_lo[i] > range_hi[i];
+ * range_hi[i] >= range_lo[i+1]; a range_output or default_output outside
+ * -1..n_outputs-1; job->n_keep_ranges > 0, n_output_shards > 1 or
+ * max_output_bytes > 0. */
+typedef struct gpuc_route_spec {
+    uint32_t n_outputs;               /* 1..32 */
+    const char* const* output_bases;  /* n_outputs path prefixes, pairwise different;
+                                         job->output_base is ignored and may be NULL */
+    uint32_t n_ranges;                /* may be 0 */
+    const int64_t* range_lo;          /* INCLUSIVE, signed compares */
+    const int64_t* range_hi;          /* INCLUSIVE; lo[i] <= hi[i], hi[i] < lo[i+1] */
+    const int32_t* range_output;      /* per range: 0..n_outputs-1, or -1 == drop */
+    int32_t default_output;           /* tokens in no range: 0..n_outputs-1, or -1 == drop */
+} gpuc_route_spec;
+
+typedef struct gpuc_route_output {
+    uint32_t written;                 /* 0: no kept partition was routed here, no file created */
+    uint64_t partitions, rows, uncompressed_bytes, compressed_bytes;
+} gpuc_route_output;
+
+int gpuc_compact_routed(const gpuc_job* job, const gpuc_route_spec* spec,
+                        gpuc_result* result,
+                        gpuc_route_output* outputs /* n_outputs entries; may be NULL */);
 
 /* Synthetic sstable generation ON THE GPU using the product write path
  * (serialize+compress+index+bloom kernels — the flush-path seed).
