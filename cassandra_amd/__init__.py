@@ -567,15 +567,26 @@ def _flush_table_parsed(S, parts, n_parts, output_base, device=0):
         raise GpuCompactError(f"gpuc_flush_table rc={rc}: {err.value.decode(errors='replace')}")
 
 
-def flush_table(memdump_path, output_base, device=0, chunk_length=0):
+def flush_table(memdump_path, output_base, device=0, chunk_length=0, ck_types=None):
     """Full-schema memtable flush: marshal an oracle .memdump (the logical
     memtable content) through gpuc_flush_table. A real host would build the
     same structs straight from its memtable.
     chunk_length: output chunk length in bytes (power of two, 1024..65536);
-    0 == 16 KiB."""
+    0 == 16 KiB.
+    ck_types: clustering type names (bytes, one per clustering column) that
+    replace the memdump's type ordinals. The memdump has no ordinal for
+    ReversedType, so this is how a table with CLUSTERING ORDER BY (... DESC) is
+    flushed from it: the unfiltereds must then be in that (descending) order."""
     with open(memdump_path, "rb") as f:
         data = f.read()
     S, parts, n_parts, bufs = _parse_memdump(data)
+    if ck_types is not None:
+        if len(ck_types) != S.n_ck:
+            raise GpuCompactError(f"ck_types has {len(ck_types)} entries for {S.n_ck} "
+                                  "clustering columns")
+        a_ckt = (ctypes.c_char_p * max(S.n_ck, 1))(*[bytes(t) for t in ck_types])
+        bufs.append(a_ckt)
+        S.ck_types = a_ckt
     S.chunk_length = chunk_length
     _flush_table_parsed(S, parts, n_parts, output_base, device)
     del bufs

@@ -559,6 +559,7 @@ struct DevSchema {
         };
         SchemaParams sch{};
         sch.n_ck = (uint32_t)hs.ck_widths.size();
+        sch.ck_desc = hs.ck_desc_mask();
         sch.ck_w = up(ck_w, hs.ck_widths);
         sch.n_cols = (uint32_t)hs.col_fixed.size();
         sch.col_fixed = up(col_fixed, hs.col_fixed);
@@ -570,6 +571,26 @@ struct DevSchema {
         return sch;
     }
 };
+
+// Rows.db keys are the byte-comparable form of the clusterings, which
+// ReversedType inverts; the BTI index of a table with a descending clustering
+// column is out of scope and refused before any Data.db byte is parsed
+static void refuse_bti_desc(const std::vector<std::string>& clustering_types, const char* what) {
+    for (auto& t : clustering_types)
+        if (ck_type(t).desc)
+            throw unsupported_error(std::string(what) + " of a table with a descending clustering "
+                                    "column (" + t + ") unsupported: Rows.db keys are the "
+                                    "byte-comparable clusterings, which ReversedType inverts");
+}
+
+// the writer and the digest kernels decode ascending clustering encodings:
+// called once, after the last comparison over `rows` (k_ck_ascending)
+static void restore_ck_ascending(const OutParts& op, const UnfColsBuf& rows, uint64_t n_groups,
+                                 const SchemaParams& sch, hipStream_t stream) {
+    if (!sch.ck_desc || !n_groups) return;
+    hipLaunchKernelGGL(k_ck_ascending, dim3((uint32_t)((n_groups + 255) / 256)), dim3(256), 0,
+                       stream, op, rows.uc, n_groups, sch);
+}
 
 // a source's own header (its counts and its maps into the union) in its SrcDesc2
 static void set_src_columns(SrcDesc2& sd, const SourceColumns& sc) {
@@ -2188,6 +2209,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             sp2.hs.min_ldt = min_ldt == NO_DELETION_TIME ? DELETION_TIME_EPOCH : min_ldt;
             sp2.hs.min_ttl = min_ttl == INT32_MAX ? 0 : min_ttl;
         }
+        restore_ck_ascending(opb.op, *rows_for_writer, n_groups, sch, stream);
         if (g_validate_out) {
             // VALIDATION epilogue: per-partition repair digests instead of a
             // written sstable (k_validate_digest; Validator.rowHash)
@@ -2515,6 +2537,7 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
         su.generations[s] = std::stoull(name.substr(a + 1, b2 - a - 1));
     }
     su.js = resolve_job_schema(su.stats, su.k_data);
+    if (su.bti) refuse_bti_desc(su.js.header.clustering_types, "a `da` (BTI) input");
     if (su.bti) {
         // positions collected from the tries above; append the end sentinel
         for (int s = 0; s < k; s++) su.positions[s].push_back(su.cinfos[s].data_len);
@@ -2740,6 +2763,7 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         const bool da = exists(base + "-Partitions.db") && !exists(base + "-Index.db");
         HCompressionInfo ci = parse_compression_info(read_file(base + "-CompressionInfo.db"));
         HStatistics st = parse_statistics(read_file(base + "-Statistics.db"));
+        if (da) refuse_bti_desc(st.clustering_types, "a `da` (BTI) input");
         bytes comp = read_file(base + "-Data.db");
         std::vector<uint64_t> positions;
         if (da) {
@@ -2983,6 +3007,7 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         sp2.hs.min_ts = st.min_timestamp == NO_TIMESTAMP ? TIMESTAMP_EPOCH : st.min_timestamp;
         sp2.hs.min_ldt = st.min_ldt == NO_DELETION_TIME ? DELETION_TIME_EPOCH : st.min_ldt;
         sp2.hs.min_ttl = st.min_ttl == INT32_MAX ? 0 : st.min_ttl;
+        restore_ck_ascending(rec.parts.op, rec.rows, groups.n, sch, stream);
         write_sstable_device(rec.parts, rec.rows, groups.n, sp2, rec.stats, d_tomb, tomb_cap, st,
                              OutputOptions{output_base, ci.snappy, false, ci.chunk_len, 0}, stream);
         return GPUC_OK;
@@ -3127,7 +3152,7 @@ static int h_bk_comparison(uint8_t k) {
 
 // ClusteringComparator.compare over two ABI unfiltereds (mirrors pos_cmp)
 static int h_unf_cmp(const gpuc_unfiltered& a, const gpuc_unfiltered& b,
-                     const std::vector<int32_t>& ckw) {
+                     const std::vector<int32_t>& ckw, uint32_t ck_desc) {
     uint32_t mn = a.ck_count < b.ck_count ? a.ck_count : b.ck_count;
     for (uint32_t c = 0; c < mn; c++) {
         int32_t w = ckw[c];
@@ -3137,12 +3162,14 @@ static int h_unf_cmp(const gpuc_unfiltered& a, const gpuc_unfiltered& b,
         uint64_t sa, sb;
         if (w > 0) { sa = h_ck_sortable(pa, w); sb = h_ck_sortable(pb, w); }
         else { sa = h_ck_prefix_var(pa, la); sb = h_ck_prefix_var(pb, lb); }
-        if (sa != sb) return sa < sb ? -1 : 1;
+        // a descending component: every value comparison negated (kinds are not)
+        const int lt = (ck_desc >> c) & 1u ? 1 : -1;
+        if (sa != sb) return sa < sb ? lt : -lt;
         if (w < 0) {
             uint32_t n = la < lb ? la : lb;
             for (uint32_t i = 8; i < n; i++)
-                if (pa[i] != pb[i]) return pa[i] < pb[i] ? -1 : 1;
-            if (la != lb) return la < lb ? -1 : 1;
+                if (pa[i] != pb[i]) return pa[i] < pb[i] ? lt : -lt;
+            if (la != lb) return la < lb ? lt : -lt;
         }
     }
     if (a.ck_count != b.ck_count)
@@ -3185,15 +3212,17 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         const std::string MAPT_PFX = "org.apache.cassandra.db.marshal.MapType";
         const std::string CTRT = "org.apache.cassandra.db.marshal.CounterColumnType";
         // the types go to the Statistics.db header as given; the widths the
-        // kernels walk with: clustering types must be known (ck_type_width
+        // kernels walk with: clustering types must be known (ck_type
         // throws), an unknown regular or static type is variable width
         TableTypes types;
         HostSchema hsch;
         types.key_type = S.key_type ? S.key_type : "org.apache.cassandra.db.marshal.BytesType";
         for (uint32_t i = 0; i < S.n_ck; i++) {
             types.clustering_types.emplace_back(S.ck_types[i]);
-            hsch.ck_widths.push_back(ck_type_width(types.clustering_types.back()));
+            hsch.add_ck(types.clustering_types.back());
         }
+        const uint32_t ck_desc_h = hsch.ck_desc_mask();
+        if (S.bti) refuse_bti_desc(types.clustering_types, "`bti` output");
         const std::vector<int32_t>& ckw_h = hsch.ck_widths;
         // n_cols in the ABI counts ALL regular columns; SchemaParams.n_cols
         // counts the SIMPLE ones (the n_cpx complex ones last, excluded)
@@ -3265,7 +3294,7 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                         }
                     }
                 }
-                if (prev && h_unf_cmp(*prev, U, ckw_h) >= 0)
+                if (prev && h_unf_cmp(*prev, U, ckw_h, ck_desc_h) >= 0)
                     throw std::runtime_error("unfiltereds out of clustering order in partition " +
                                              std::to_string(p));
                 prev = &U;
@@ -3412,6 +3441,8 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                 const gpuc_unfiltered& U = P.unf[r];
                 h_rkind[ob] = U.kind;
                 h_ckcnt[ob] = U.ck_count;
+                // ascending encodings whatever the direction: the order was
+                // checked on the host (h_unf_cmp) and the device only writes
                 for (uint32_t c = 0; c < U.ck_count; c++) {
                     uint64_t oc = ob * NCK + c;
                     int32_t w = ckw_h[c];

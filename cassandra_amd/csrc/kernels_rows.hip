@@ -31,6 +31,7 @@ __device__ inline void tomb_push(OutStats* st, uint32_t* ldts, uint32_t cap, uin
 // lists is in its SrcDesc2.
 struct SchemaParams {
     uint32_t n_ck;           // clustering columns (0..32)
+    uint32_t ck_desc;        // bit c: clustering column c descends (ReversedType)
     const int32_t* ck_w;     // per clustering column: 4/8 fixed or -1 variable
     uint32_t n_cols;         // SIMPLE regular columns (1..63; header order)
     const int32_t* col_fixed;  // per simple column: -1 variable else fixed width
@@ -63,9 +64,38 @@ __device__ inline uint64_t ck_prefix_var(const uint8_t* p, uint32_t len) {
     for (uint32_t b = 0; b < n; b++) v |= (uint64_t)p[b] << (8 * (7 - b));
     return v;
 }
+// Direction of a clustering column is folded into the encoding: a descending
+// (ReversedType) component stores the COMPLEMENT of the ascending encoding
+// (for variable width, of the zero-padded prefix, so a shorter value sorts
+// after its extensions). Every component still orders by one u64 compare;
+// only the variable-width tie-break looks at the direction. The writer and
+// the digest kernels decode ASCENDING encodings: k_ck_ascending takes the
+// complement back out once the last comparison is done.
+__device__ inline uint64_t ck_dir(uint32_t ck_desc, uint32_t c) {
+    return 0ull - (uint64_t)((ck_desc >> c) & 1u);
+}
 __device__ inline void ck_bytes(uint64_t ck, int width, uint8_t* out) {
     uint64_t v = ck ^ (1ULL << (8 * width - 1));
     for (int b = 0; b < width; b++) out[b] = (uint8_t)(v >> (8 * (width - 1 - b)));
+}
+// Runs between the last position comparison (merge, garbage filter) and the
+// writer or digest kernels, for tables with a descending clustering column
+// only (ck_desc != 0): takes the complement back out of the fixed-width
+// components of every kept group's unfiltereds, so that ck_bytes and the
+// digest decode what they always did and the ascending path's writer code is
+// the same instruction stream as without the feature. Variable-width
+// components are written from ck_addr and keep their complemented prefix.
+__global__ void k_ck_ascending(OutParts op, UnfCols out, uint64_t n, SchemaParams sch) {
+    uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n || !op.keep[g]) return;
+    uint64_t base = op.row_base[g];
+    uint32_t cnt = op.row_count[g];
+    for (uint32_t i = 0; i < cnt; i++) {
+        uint64_t o = base + i;
+        uint32_t nv = out.ck_count[o];
+        for (uint32_t c = 0; c < nv; c++)
+            if (sch.ck_w[c] > 0) out.ck[o * sch.n_ck + c] ^= ck_dir(sch.ck_desc, c);
+    }
 }
 // Kind.comparedToClustering (ClusteringPrefix.java): placement of a
 // SHORTER prefix (bound) against longer prefixes sharing its components
@@ -75,20 +105,23 @@ __device__ inline int bk_cmp_to_clustering(uint8_t kk) {
 }
 // one clustering component (typed): fixed widths compare via the sortable
 // u64; variable widths compare prefix then byte-walk (unsigned lex,
-// shorter-first)
-__device__ inline int ck_cmp_component(const UnfCols& u, uint64_t ac, uint64_t bc, int32_t w) {
+// shorter-first). A descending component's u64 already carries its
+// direction; its tie-break past the prefix is negated here.
+__device__ inline int ck_cmp_component(const UnfCols& u, uint64_t ac, uint64_t bc, int32_t w,
+                                       bool desc) {
     uint64_t pa = u.ck[ac], pb = u.ck[bc];
     if (pa != pb) return pa < pb ? -1 : 1;
     if (w >= 0) return 0;
+    const int lt = desc ? 1 : -1;
     uint32_t la = u.ck_len[ac], lb = u.ck_len[bc];
     if (la > 8 || lb > 8) {
         const uint8_t* a8 = (const uint8_t*)u.ck_addr[ac];
         const uint8_t* b8 = (const uint8_t*)u.ck_addr[bc];
         uint32_t n = la < lb ? la : lb;
         for (uint32_t i = 8; i < n; i++)
-            if (a8[i] != b8[i]) return a8[i] < b8[i] ? -1 : 1;
+            if (a8[i] != b8[i]) return a8[i] < b8[i] ? lt : -lt;
     }
-    return la == lb ? 0 : (la < lb ? -1 : 1);
+    return la == lb ? 0 : (la < lb ? lt : -lt);
 }
 // ClusteringComparator over full prefixes (compare_clustering_prefix in the
 // oracle; ClusteringComparator.compare in the reference): component-wise,
@@ -98,7 +131,8 @@ __device__ inline int pos_cmp(const UnfCols& in, uint64_t a, uint64_t b, const S
         uint32_t na = in.ck_count[a], nb = in.ck_count[b];
         uint32_t mn = na < nb ? na : nb;
         for (uint32_t c = 0; c < mn; c++) {
-            int r = ck_cmp_component(in, a * sch.n_ck + c, b * sch.n_ck + c, sch.ck_w[c]);
+            int r = ck_cmp_component(in, a * sch.n_ck + c, b * sch.n_ck + c, sch.ck_w[c],
+                                     (sch.ck_desc >> c) & 1u);
             if (r) return r;
         }
         if (na != nb)
@@ -338,11 +372,11 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
                 uint64_t oc = o * sp.n_ck + c;
                 uint32_t cklen;
                 if (sp.ck_w[c] > 0) {
-                    rc.ck[oc] = ck_sortable(base + pos, sp.ck_w[c]);
+                    rc.ck[oc] = ck_sortable(base + pos, sp.ck_w[c]) ^ ck_dir(sp.ck_desc, c);
                     cklen = (uint32_t)sp.ck_w[c];
                 } else {
                     cklen = (uint32_t)uvint_get(base, &pos);
-                    rc.ck[oc] = ck_prefix_var(base + pos, cklen);
+                    rc.ck[oc] = ck_prefix_var(base + pos, cklen) ^ ck_dir(sp.ck_desc, c);
                 }
                 rc.ck_addr[oc] = (uint64_t)(base + pos);
                 rc.ck_len[oc] = cklen;
@@ -386,11 +420,11 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
                 uint64_t oc = o * sp.n_ck + c;
                 uint32_t cklen;
                 if (sp.ck_w[c] > 0) {
-                    rc.ck[oc] = ck_sortable(base + pos, sp.ck_w[c]);
+                    rc.ck[oc] = ck_sortable(base + pos, sp.ck_w[c]) ^ ck_dir(sp.ck_desc, c);
                     cklen = (uint32_t)sp.ck_w[c];
                 } else {
                     cklen = (uint32_t)uvint_get(base, &pos);
-                    rc.ck[oc] = ck_prefix_var(base + pos, cklen);
+                    rc.ck[oc] = ck_prefix_var(base + pos, cklen) ^ ck_dir(sp.ck_desc, c);
                 }
                 rc.ck_addr[oc] = (uint64_t)(base + pos);
                 rc.ck_len[oc] = cklen;
@@ -3040,15 +3074,16 @@ __device__ inline int pos_cmp2(const UnfCols& A, uint64_t a, const UnfCols& B, u
             uint64_t pa = A.ck[ac], pb = B.ck[bc];
             if (pa != pb) return pa < pb ? -1 : 1;
             if (sch.ck_w[c] < 0) {
+                const int lt = (sch.ck_desc >> c) & 1u ? 1 : -1;  // descending: negated
                 uint32_t la = A.ck_len[ac], lb = B.ck_len[bc];
                 if (la > 8 || lb > 8) {
                     const uint8_t* a8 = (const uint8_t*)A.ck_addr[ac];
                     const uint8_t* b8 = (const uint8_t*)B.ck_addr[bc];
                     uint32_t n = la < lb ? la : lb;
                     for (uint32_t i = 8; i < n; i++)
-                        if (a8[i] != b8[i]) return a8[i] < b8[i] ? -1 : 1;
+                        if (a8[i] != b8[i]) return a8[i] < b8[i] ? lt : -lt;
                 }
-                if (la != lb) return la < lb ? -1 : 1;
+                if (la != lb) return la < lb ? lt : -lt;
             }
         }
         if (na != nb)

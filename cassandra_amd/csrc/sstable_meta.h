@@ -268,8 +268,12 @@ inline void parse_index_positions(const bytes& ib, uint64_t data_len,
 // marshal type string -> serialized value width, -1 variable. Permissive: a
 // type it does not know is variable width; callers that must refuse unknown
 // types check simple_value_type first.
+// TimestampType is an 8-byte value compared as a signed long
+// (valueLengthIfFixed() == 8, compareCustom == LongType.compareLongs): both
+// recalled, not checked against the Java sources.
 inline int32_t type_width(const std::string& t) {
     if (t == "org.apache.cassandra.db.marshal.LongType") return 8;
+    if (t == "org.apache.cassandra.db.marshal.TimestampType") return 8;
     if (t == "org.apache.cassandra.db.marshal.Int32Type") return 4;
     return -1;
 }
@@ -279,15 +283,52 @@ inline bool simple_value_type(const std::string& t) {
            t == "org.apache.cassandra.db.marshal.AsciiType" ||
            t == "org.apache.cassandra.db.marshal.BytesType";
 }
-// clustering component width; refuses every other type
+// clustering component width of a plain (ascending) type; refuses every other
 inline int32_t ck_type_width(const std::string& t) {
     if (!simple_value_type(t)) throw std::runtime_error("unsupported clustering type " + t);
     return type_width(t);
+}
+// A clustering type is a simple value type T or ReversedType(T), the type of
+// a column declared CLUSTERING ORDER BY (... DESC). ReversedType reverses the
+// comparison of VALUES only and serializes as T does (valueLengthIfFixed
+// delegates to the base type). Refuses every other type, a nested
+// ReversedType included, with the type string in the message.
+struct CkType {
+    int32_t width;  // of the inner type: 4/8 fixed, -1 variable
+    bool desc;
+};
+static const std::string REVERSED_PFX = "org.apache.cassandra.db.marshal.ReversedType(";
+inline bool reversed_type(const std::string& t) {
+    return t.compare(0, REVERSED_PFX.size(), REVERSED_PFX) == 0;
+}
+inline CkType ck_type(const std::string& t) {
+    if (reversed_type(t)) {
+        if (t.back() != ')') throw unsupported_error("unsupported clustering type " + t);
+        const std::string inner =
+            t.substr(REVERSED_PFX.size(), t.size() - REVERSED_PFX.size() - 1);
+        if (!simple_value_type(inner)) throw unsupported_error("unsupported clustering type " + t);
+        return {type_width(inner), true};
+    }
+    if (!simple_value_type(t)) throw unsupported_error("unsupported clustering type " + t);
+    return {type_width(t), false};
 }
 
 struct HostSchema {
     std::vector<int32_t> col_fixed;     // SIMPLE regular columns only
     std::vector<int32_t> ck_widths;     // per clustering column
+    std::vector<uint8_t> ck_desc;       // per clustering column: 1 = descending (ReversedType)
+    // bit c set == clustering column c descends (at most 32 columns)
+    uint32_t ck_desc_mask() const {
+        uint32_t m = 0;
+        for (size_t c = 0; c < ck_desc.size() && c < 32; c++)
+            if (ck_desc[c]) m |= 1u << c;
+        return m;
+    }
+    void add_ck(const std::string& t) {
+        CkType k = ck_type(t);
+        ck_widths.push_back(k.width);
+        ck_desc.push_back(k.desc ? 1 : 0);
+    }
     std::vector<int32_t> static_fixed;  // per static column
     uint32_t n_cpx = 0;                 // trailing complex (map<blob,blob>) columns
     bool counters = false;              // counter table (every column CounterColumnType)
@@ -298,6 +339,14 @@ struct HostSchema {
 inline HostSchema resolve_schema(const HStatistics& st) {
     HostSchema hs;
     const auto& rcols = st.regular_cols;
+    // ReversedType belongs to clustering columns alone
+    auto reversed = [](const std::string& t) { return reversed_type(t); };
+    if (reversed(st.key_type)) throw unsupported_error("unsupported partition key type " + st.key_type);
+    for (auto& c : rcols)
+        if (reversed(c.second)) throw unsupported_error("unsupported column type " + c.second);
+    for (auto& c : st.static_cols)
+        if (reversed(c.second))
+            throw unsupported_error("unsupported static column type " + c.second);
     const std::string map_bb =
         "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,"
         "org.apache.cassandra.db.marshal.BytesType)";
@@ -335,7 +384,7 @@ inline HostSchema resolve_schema(const HStatistics& st) {
         if (!st.static_cols.empty())
             throw std::runtime_error("static columns with counters unsupported");
     }
-    for (auto& t : st.clustering_types) hs.ck_widths.push_back(ck_type_width(t));
+    for (auto& t : st.clustering_types) hs.add_ck(t);
     for (auto& sc : st.static_cols) {
         if (!simple_value_type(sc.second))
             throw std::runtime_error("unsupported static column type " + sc.second);

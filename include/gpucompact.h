@@ -5,8 +5,9 @@
  * (reference: src/java/org/apache/cassandra/db/compaction/CompactionTask.java:184-236)
  * — scanners + CompactionIterator + CompactionAwareWriter — for eligible
  * tables (big-format `oa`, Murmur3Partitioner, any partition key, up to 32
- * clustering columns of fixed (bigint/int) or variable (text/ascii/blob)
- * width including prefix range-tombstone bounds, 1..63 regular and 1..63
+ * clustering columns of fixed (bigint/int/timestamp) or variable
+ * (text/ascii/blob) width, each ascending or descending, including prefix
+ * range-tombstone bounds, 1..63 regular and 1..63
  * static columns with cell subsets, LZ4 or Snappy chunk compression with any
  * power-of-two chunk_length_in_kb from 1 to 64 KiB — inputs of one job may
  * mix lengths; row, cell, partition and range tombstones all supported).
@@ -14,6 +15,30 @@
  * byU16 table at 65547 input bytes and snappy splits into several 64 KiB
  * fragments: different algorithms); a zero or non-power-of-two length in a
  * CompressionInfo.db is GPUC_ERR_FORMAT.
+ *
+ * Clustering types. A clustering column's type string is one of LongType,
+ * Int32Type, TimestampType, UTF8Type, AsciiType, BytesType, or
+ * org.apache.cassandra.db.marshal.ReversedType(T) with T one of those six: a
+ * column declared CLUSTERING ORDER BY (... DESC). ReversedType reverses the
+ * comparison of values, never the bound kinds, and serializes as T does
+ * (ReversedType.valueLengthIfFixed delegates to its base type); the exact
+ * string of the inputs goes into the output's HEADER and STATS components
+ * unchanged, and all inputs of a job carry equal strings (one input ascending
+ * and one descending over the same base type is refused). TimestampType is
+ * also accepted as a simple regular or static column type. It is taken as an
+ * 8-byte fixed-width value compared as a signed long:
+ * TimestampType.valueLengthIfFixed() == 8 and compareCustom ==
+ * LongType.compareLongs are recalled, not checked against the Java sources.
+ * GPUC_ERR_UNSUPPORTED with the type string in the message: a nested
+ * ReversedType(ReversedType(...)), ReversedType of any other inner type, any
+ * other clustering type, and ReversedType as key type or as a regular or
+ * static column type. A `da` (BTI) input, or `bti` output, of a table with a
+ * descending clustering column is GPUC_ERR_UNSUPPORTED before any Data.db
+ * byte is parsed: Rows.db keys are the byte-comparable form of the
+ * clusterings, which ReversedType inverts. `da` tables without a descending
+ * clustering column are unaffected. gpuc_flush_table takes the ReversedType
+ * strings in ck_types and checks the unfiltereds of each partition under that
+ * comparator: ascending rows under a descending type are an error.
  *
  * The inputs of one job may list different columns in their serialization
  * headers (sstables older than an ALTER TABLE ... ADD, flushes that held only
