@@ -406,7 +406,10 @@ class _MemdumpReader:
         return f, self.i64(), self.i32(), self.i64(), self.i64(), self.u32()
 
 
-def _parse_memdump(data):
+def _parse_memdump(data, col_types=None):
+    """col_types: {column name: marshal type string} replacing the type the
+    memdump's ordinal stands for (regular and static columns by name)."""
+    col_types = {bytes(k): bytes(v) for k, v in (col_types or {}).items()}
     r = _MemdumpReader(data)
     if data[:4] != b"GMD2":
         raise GpuCompactError("bad memdump magic")
@@ -420,6 +423,14 @@ def _parse_memdump(data):
     cols = [(r.blob(), r.u8()) for _ in range(n_cols)]
     n_cpx = sum(1 for _, t in cols if t == 5)
     cols = [(nm, _CQL_TYPE_NAMES[t]) for nm, t in cols]
+    # the memdump's complex columns are found by their ordinal, before a type
+    # override renames them (the layout of the cells is the same)
+    cpx_idx = [i for i, (_, t) in enumerate(cols) if b"MapType" in t]
+    unknown = set(col_types) - {nm for nm, _ in cols} - {nm for nm, _ in statics}
+    if unknown:
+        raise GpuCompactError(f"col_types names no column of the memdump: {sorted(unknown)}")
+    cols = [(nm, col_types.get(nm, t)) for nm, t in cols]
+    statics = [(nm, col_types.get(nm, t)) for nm, t in statics]
     snappy = r.u8()
     bti = r.u8()
     cis = r.u32()
@@ -452,7 +463,6 @@ def _parse_memdump(data):
     S.has_stats = 1
     S.stats_min_ts, S.stats_min_ldt, S.stats_min_ttl = stats_ts, stats_ldt, stats_ttl
     n_simple = n_cols - n_cpx
-    cpx_idx = [i for i, (_, t) in enumerate(cols) if b"MapType" in t]
 
     parts = (GpucFlushPart * n_parts)()
     for pi in range(n_parts):
@@ -567,7 +577,8 @@ def _flush_table_parsed(S, parts, n_parts, output_base, device=0):
         raise GpuCompactError(f"gpuc_flush_table rc={rc}: {err.value.decode(errors='replace')}")
 
 
-def flush_table(memdump_path, output_base, device=0, chunk_length=0, ck_types=None):
+def flush_table(memdump_path, output_base, device=0, chunk_length=0, ck_types=None,
+                col_types=None):
     """Full-schema memtable flush: marshal an oracle .memdump (the logical
     memtable content) through gpuc_flush_table. A real host would build the
     same structs straight from its memtable.
@@ -576,10 +587,16 @@ def flush_table(memdump_path, output_base, device=0, chunk_length=0, ck_types=No
     ck_types: clustering type names (bytes, one per clustering column) that
     replace the memdump's type ordinals. The memdump has no ordinal for
     ReversedType, so this is how a table with CLUSTERING ORDER BY (... DESC) is
-    flushed from it: the unfiltereds must then be in that (descending) order."""
+    flushed from it: the unfiltereds must then be in that (descending) order.
+    col_types: {column name: type name} (bytes) replacing the type of the named
+    regular or static columns, the twin of ck_types. The memdump knows one
+    collection type, map<blob,blob>; this is how a set<int> or a
+    map<bigint,text> column is flushed from it (its cells must then be in the
+    order of that key type, a set's cells without values), and how a blob
+    column becomes a FrozenType(...) one."""
     with open(memdump_path, "rb") as f:
         data = f.read()
-    S, parts, n_parts, bufs = _parse_memdump(data)
+    S, parts, n_parts, bufs = _parse_memdump(data, col_types)
     if ck_types is not None:
         if len(ck_types) != S.n_ck:
             raise GpuCompactError(f"ck_types has {len(ck_types)} entries for {S.n_ck} "

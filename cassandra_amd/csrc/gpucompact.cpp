@@ -494,6 +494,15 @@ static unsigned long long read_dev_error(const DevBuf& d_error, hipStream_t stre
     HIP_CHECK(hipMemcpy(&err, d_error.p, 8, hipMemcpyDeviceToHost));
     return err;
 }
+// the collection-type checks of k_parse_rows (codes 19, 26): GPUC_ERR_FORMAT
+static void throw_if_collection_parse_error(unsigned long long err) {
+    if (err == 19)
+        throw format_error("Data.db: a cell path of a collection with int, bigint or timestamp "
+                           "keys does not have the width of its key type (parse error code 19)");
+    if (err == 26)
+        throw format_error("Data.db: a cell of a set column carries a value "
+                           "(parse error code 26)");
+}
 
 // validated frames -> decoder descriptors. d_comp holds the file's bytes
 // from offset comp_lo on; chunk i of the window decodes to d_out + i * chunk_len.
@@ -592,6 +601,11 @@ static void restore_ck_ascending(const OutParts& op, const UnfColsBuf& rows, uin
                        stream, op, rows.uc, n_groups, sch);
 }
 
+// the collection-type masks of a schema's complex columns (kernels_rows.hip)
+static CpxTypes cpx_types(const HostSchema& hs) {
+    return CpxTypes{hs.cpx_key_signed_mask(), hs.cpx_key_w8_mask(), hs.cpx_is_set_mask()};
+}
+
 // a source's own header (its counts and its maps into the union) in its SrcDesc2
 static void set_src_columns(SrcDesc2& sd, const SourceColumns& sc) {
     sd.n_cols = sc.n_cols;
@@ -617,12 +631,20 @@ struct ParsedInput {
     UnfColsBuf rows;
     ParsedCols pc{};
     uint64_t total_rows = 0, total_cpx = 0;
+    CpxTypes cx{};  // of the schema it was parsed under; the merge reads it too
 };
 // The parse chain for n_srcs sources over `total` partitions. Pass A
 // (k_parse_count) fills the merge records and partition columns; count_only
 // (verify) stops there and leaves pc.st empty. Then row counts are scanned
 // into row bases, the complex cells are counted and scanned when the schema
-// has a complex column, and pass B (k_parse_rows) decodes the rows.
+// has a complex column, and pass B (k_parse_rows) decodes the rows. The
+// caller sets in.cx (cpx_types of the schema) first when the schema has typed
+// or set collection columns.
+// CONTRACT: a partition that either pass rejects ends its walk at once and
+// leaves its remaining row slots (and the counts of the column it stopped in)
+// unwritten. Every caller reads d_error (read_dev_error) after this returns
+// and before ANYTHING consumes in.rows or in.pc; compaction, scrub and verify
+// all throw there.
 static void parse_input(ParsedInput& in, const DevBuf& d_srcs, uint32_t n_srcs, uint64_t total,
                         const DevBuf& d_recs, const SchemaParams& sch, const DevBuf& d_error,
                         const DevBuf& d_rows_in, bool count_only, hipStream_t stream) {
@@ -652,9 +674,12 @@ static void parse_input(ParsedInput& in, const DevBuf& d_srcs, uint32_t n_srcs, 
     if (read_dev_error(d_error, stream)) return;
     in.rows.alloc(in.total_rows, sch.n_cols, sch.n_ck, sch.n_cpx);
     if (!total) return;
+    // byte-ordered tables launch the walk without the collection checks
+    const bool typed = in.cx.key_signed || in.cx.is_set;
     auto rows_pass = [&](const uint64_t* cpx_bases) {
-        hipLaunchKernelGGL(k_parse_rows, grid, block, 0, stream, srcs, n_srcs, (uint32_t)total, pc,
-                           in.rows.uc, sch, err, d_rows_in.as<unsigned long long>(), cpx_bases);
+        hipLaunchKernelGGL(typed ? k_parse_rows<true> : k_parse_rows<false>, grid, block, 0, stream,
+                           srcs, n_srcs, (uint32_t)total, pc, in.rows.uc, sch, in.cx, err,
+                           d_rows_in.as<unsigned long long>(), cpx_bases);
     };
     if (sch.n_cpx) {
         // counting pass: full walk, per-partition complex-cell totals, which
@@ -744,7 +769,8 @@ static void launch_reconcile(const Groups& g, int n_sources, const DevBuf& d_src
         hipLaunchKernelGGL(kern, dim3((uint32_t)((g.n + 255) / 256)), dim3(256), 0, stream,
                            g.sorted, g.start.as<uint64_t>(), g.n, g.n_recs,
                            d_srcbases.as<uint32_t>(), in.pc, in.rows.uc, out.parts.op,
-                           out.rows.uc, g.rows.as<uint64_t>(), sch, pp, out.stats.as<OutStats>(),
+                           out.rows.uc, g.rows.as<uint64_t>(), sch, in.cx, pp,
+                           out.stats.as<OutStats>(),
                            d_error.as<unsigned long long>());
     };
     if (n_sources <= 8) launch(k_reconcile_rows<8>);
@@ -1911,6 +1937,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         d_rows_in.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
         ParsedInput parsed;
+        parsed.cx = cpx_types(su.js.schema);
         parse_input(parsed, d_srcs, (uint32_t)k, total_parts, d_recs_a, sch, d_error, d_rows_in,
                     false, stream);
         const ParsedCols& pc = parsed.pc;
@@ -1920,6 +1947,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
             unsigned long long err = read_dev_error(d_error, stream);
             TR("parse synced");
             check_cancel(job);  // a set cancel flag takes precedence over a parse error
+            throw_if_collection_parse_error(err);
             if (err) throw std::runtime_error("GPU decode/parse error code " + std::to_string(err));
             uint64_t rows_in_local = 0;
             HIP_CHECK(hipMemcpy(&rows_in_local, d_rows_in.p, 8, hipMemcpyDeviceToHost));
@@ -2173,7 +2201,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                 uint32_t blocks_g = (uint32_t)((n_groups + 255) / 256);
                 hipLaunchKernelGGL(k_garbage_filter, dim3(blocks_g), dim3(256), 0, stream, opb.op,
                                    n_groups, opb_t.op, out_rows.uc, out_rows_t.uc, gc_rows.uc,
-                                   d_tidx.as<int64_t>(), d_cap.as<uint64_t>(), sch,
+                                   d_tidx.as<int64_t>(), d_cap.as<uint64_t>(), sch, parsed.cx,
                                    job->cell_level_gc ? 1 : 0);
             }
             // reset first/last group, then the deferred purge pass
@@ -2840,9 +2868,22 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         d_src.alloc(sizeof(src));
         HIP_CHECK(hipMemcpyAsync(d_src.p, &src, sizeof(src), hipMemcpyHostToDevice, stream));
         d_recs.alloc((n_parts + 1) * sizeof(MRec));
-        // pass A only: it walks every row's structure; nothing here needs the rows
+        // pass A only: it walks every row's structure; nothing here needs the
+        // rows. A set column or a collection with int, bigint or timestamp
+        // keys adds checks that only the cell walk of pass B makes (path
+        // widths, no value in a set cell): such a table gets the full parse.
+        const CpxTypes cx = cpx_types(hsch);
+        const bool cell_checks = cx.key_signed || cx.is_set;
+        DevBuf d_rows_in;
+        if (cell_checks) {
+            d_rows_in.alloc(8);
+            HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
+        }
         ParsedInput parsed;
-        parse_input(parsed, d_src, 1u, n_parts, d_recs, sch, d_error, DevBuf(), true, stream);
+        parsed.cx = cx;
+        parse_input(parsed, d_src, 1u, n_parts, d_recs, sch, d_error, d_rows_in, !cell_checks,
+                    stream);
+        if (cell_checks) throw_if_collection_parse_error(read_dev_error(d_error, stream));
         const ParsedCols& pc = parsed.pc;
         uint32_t blocks = (uint32_t)((n_parts + 255) / 256);
         if (n_parts) {
@@ -2971,9 +3012,12 @@ extern "C" int gpuc_scrub(const char* input_base, const char* output_base, int32
         d_rows_in.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
         ParsedInput parsed;
+        parsed.cx = cpx_types(hsch);
         parse_input(parsed, d_src, 1u, n_kept, d_recs, sch, d_error, d_rows_in, false, stream);
-        if (unsigned long long e = read_dev_error(d_error, stream))
+        if (unsigned long long e = read_dev_error(d_error, stream)) {
+            throw_if_collection_parse_error(e);
             throw std::runtime_error("scrub parse failed, code " + std::to_string(e));
+        }
         // single source: records are already in DecoratedKey order
         KeyLut lut{};
         lut.base[0] = d_data.as<uint8_t>();
@@ -3186,12 +3230,9 @@ static gpuc_cpx_col cpx_col_of(const gpuc_unfiltered& U, uint32_t x) {
         return gpuc_cpx_col{1, U.cpx_del_mfda, U.cpx_del_ldt, U.n_cpx_cells, U.cpx_cells};
     return gpuc_cpx_col{0, INT64_MIN, LDT_NONE_U32, 0, nullptr};
 }
-// CellPath order of map<blob,blob> keys: unsigned bytes, shorter first
-static int h_path_cmp(const gpuc_cpx_cell& a, const gpuc_cpx_cell& b) {
-    uint32_t n = a.path_len < b.path_len ? a.path_len : b.path_len;
-    int c = n ? memcmp(a.path, b.path, n) : 0;
-    if (c) return c;
-    return a.path_len == b.path_len ? 0 : (a.path_len < b.path_len ? -1 : 1);
+// CellPath order of the column's key type: the function the kernels run (cell_path.h)
+static int h_path_cmp(const gpuc_cpx_cell& a, const gpuc_cpx_cell& b, bool key_signed) {
+    return cell_path_cmp(a.path, a.path_len, b.path, b.path_len, key_signed);
 }
 
 }  // namespace flushv2
@@ -3209,7 +3250,6 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
             throw std::runtime_error("1..63 columns supported");
         if (S.n_cpx > S.n_cols) throw std::runtime_error("n_cpx exceeds n_cols");
         if (S.n_ck > 32) throw std::runtime_error("at most 32 clustering columns");
-        const std::string MAPT_PFX = "org.apache.cassandra.db.marshal.MapType";
         const std::string CTRT = "org.apache.cassandra.db.marshal.CounterColumnType";
         // the types go to the Statistics.db header as given; the widths the
         // kernels walk with: clustering types must be known (ck_type
@@ -3228,18 +3268,19 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
         // counts the SIMPLE ones (the n_cpx complex ones last, excluded)
         const uint32_t NSIMPLE = S.n_cols - S.n_cpx;
         const uint32_t NX = S.n_cpx;
-        hsch.n_cpx = S.n_cpx;
         for (uint32_t i = 0; i < S.n_cols; i++) {
             std::string t(S.col_types[i]);
-            bool is_map = t.compare(0, MAPT_PFX.size(), MAPT_PFX) == 0;
-            if (is_map != (i >= NSIMPLE))
+            if (multicell_type(t) != (i >= NSIMPLE))
                 throw std::runtime_error(
-                    "the complex (MapType) columns must be the last n_cpx regular columns");
+                    "the complex (set, map) columns must be the last n_cpx regular columns");
             if (t == CTRT) hsch.counters = true;
             types.regular_cols.emplace_back(
                 bytes(S.col_names[i], S.col_names[i] + S.col_name_lens[i]), t);
             if (i < NSIMPLE) hsch.col_fixed.push_back(type_width(t));
+            else hsch.add_cpx(collection_type(t));  // throws for the refused types
         }
+        // complex column x, by name, for the messages of the checks below
+        auto cpx_label = [&](uint32_t x) { return column_label(types.regular_cols[NSIMPLE + x].first); };
         for (uint32_t i = 0; i < S.n_static; i++) {
             std::string t(S.static_types[i]);
             types.static_cols.emplace_back(
@@ -3287,10 +3328,22 @@ extern "C" int gpuc_flush_table(const gpuc_flush_schema* schema, const gpuc_flus
                         for (uint32_t e = 0; e < X.n_cells; e++) {
                             const gpuc_cpx_cell& C = X.cells[e];
                             val_bytes += C.path_len + C.cell.value_len;
-                            if (e && h_path_cmp(X.cells[e - 1], C) >= 0)
+                            if (hsch.cpx_key_w[x] && C.path_len != hsch.cpx_key_w[x])
+                                throw std::runtime_error(
+                                    "cell path of " + std::to_string(C.path_len) +
+                                    " bytes in column " + cpx_label(x) + ", whose key type is " +
+                                    std::to_string(hsch.cpx_key_w[x]) + " bytes wide, in partition " +
+                                    std::to_string(p));
+                            // the writer sets the empty-value flag by length
+                            if (hsch.cpx_set[x] && C.cell.value_len)
+                                throw std::runtime_error("cell with a value in set column " +
+                                                         cpx_label(x) + ", in partition " +
+                                                         std::to_string(p));
+                            if (e && h_path_cmp(X.cells[e - 1], C, hsch.cpx_key_w[x] != 0) >= 0)
                                 throw std::runtime_error(
                                     "complex cells out of CellPath order in partition " +
-                                    std::to_string(p) + ", complex column " + std::to_string(x));
+                                    std::to_string(p) + ", complex column " + std::to_string(x) +
+                                    " " + cpx_label(x));
                         }
                     }
                 }

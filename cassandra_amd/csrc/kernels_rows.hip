@@ -18,6 +18,7 @@
 #include "gpu_structs.h"
 #include "merkle_spec.h"
 #include "route_spec.h"
+#include "cell_path.h"
 
 namespace gpuc {
 
@@ -48,6 +49,21 @@ struct SchemaParams {
     // counter schemas exclude complex columns)
     uint32_t counters;
     uint8_t* ctr_arena;
+};
+// Collection types of the schema's complex columns, bit x == complex column x
+// (cell_path.h; at most 63, so masks suffice and no device table is needed):
+// the cell paths compare signed (Int32Type / LongType / TimestampType keys)
+// and are exactly 4 bytes wide, or 8 where key_w8 is set; the column is a
+// set, whose cells carry no value. All zero == every complex column orders
+// its paths as unsigned bytes. Passed by value, the way ck_desc is, but as an
+// argument of its own to the three kernels that read it (k_parse_rows,
+// k_reconcile_rows, k_garbage_filter): SchemaParams, and SerParams2 which
+// embeds it, keep their layout, so every other kernel is launched exactly as
+// before these types.
+struct CpxTypes {
+    uint64_t key_signed;
+    uint64_t key_w8;
+    uint64_t is_set;
 };
 
 // sortable ck encoding: big-endian fixed-width signed value -> flip sign bit
@@ -258,8 +274,13 @@ __global__ void k_parse_count(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t to
 // cpx_base: per-partition bases into the complex-cell arena (exscan of
 // pc.cpx_total). nullptr = COUNT mode: walk everything, fill all non-arena
 // outputs, and write pc.cpx_total[gi] for the sizing exscan.
+// TYPED: the schema has a signed-key or a set column (cx has a bit set), and
+// the complex-cell walk checks path widths and set values. Tables whose
+// complex columns are all byte-ordered maps launch the <false> instantiation,
+// which never reads cx and is the walk as it was before these types.
+template <bool TYPED>
 __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t total,
-                             ParsedCols pc, UnfCols rc, SchemaParams sp,
+                             ParsedCols pc, UnfCols rc, SchemaParams sp, CpxTypes cx,
                              unsigned long long* error, unsigned long long* rows_in,
                              const uint64_t* cpx_base = nullptr) {
     uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
@@ -512,6 +533,10 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
                     }
                     uint32_t ncc = (uint32_t)uvint_get(base, &pos);
                     rc.cpx_count[ox] = ncc;
+                    // collection type of this column: the path width it
+                    // enforces (0 = any) and whether its cells carry no value
+                    const uint32_t key_w = TYPED ? cpx_key_width(cx.key_signed, cx.key_w8, x) : 0u;
+                    const bool is_set = TYPED && cpx_bit(cx.is_set, x);
                     for (uint32_t e = 0; e < ncc; e++) {
                         uint8_t cf = base[pos++];
                         int64_t cts = (cf & 8) ? lts : (int64_t)uvint_get(base, &pos) + sd.min_ts;
@@ -522,6 +547,18 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
                         else ldtl = NO_DELETION_TIME;
                         int32_t cttl = (cf & 16) ? lttl : (exp ? (int32_t)(uint32_t)uvint_get(base, &pos) + sd.min_ttl : 0);
                         uint32_t plen = (uint32_t)uvint_get(base, &pos);  // CellPath vint+bytes
+                        // A signed-key path of another width (an empty one
+                        // included) has no place in the typed order, and a
+                        // set cell with a value cannot be walked (EmptyType
+                        // reads zero bytes): both end the walk of this
+                        // partition here. The cells written so far are the
+                        // count the arena sizing gets, so the fill pass,
+                        // which stops at the same cell, stays inside it.
+                        if (TYPED && ((key_w && plen != key_w) || (is_set && !(cf & 4)))) {
+                            atomicExch(error, is_set && !(cf & 4) ? 26ull : 19ull);
+                            if (pc.cpx_total) pc.cpx_total[gi] = cpx_seen + e;
+                            return;
+                        }
                         uint64_t paddr = (uint64_t)(base + pos);
                         pos += plen;
                         uint64_t vaddr = 0;
@@ -564,7 +601,6 @@ __global__ void k_parse_rows(const SrcDesc2* srcs, uint32_t n_srcs, uint32_t tot
     }
     if (rows_local) atomicAdd(rows_in, rows_local);  // one atomic per partition
     if (sp.n_cpx && pc.cpx_total) pc.cpx_total[gi] = cpx_seen;
-    (void)error;
 }
 
 // MurmurHash.hash2_64 (utils/MurmurHash.java:96-150), the COMPACTION-HLL
@@ -1072,7 +1108,7 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                                  uint64_t n_groups, uint64_t n_recs,
                                  const uint32_t* src_bases, ParsedCols pc, UnfCols in,
                                  OutParts op, UnfCols out, const uint64_t* out_base,
-                                 SchemaParams sp, PurgeParams2 pp, OutStats* st,
+                                 SchemaParams sp, CpxTypes cx, PurgeParams2 pp, OutStats* st,
                                  unsigned long long* error) {
     uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_groups) return;
@@ -1768,9 +1804,13 @@ __global__ void k_reconcile_rows(const MRec* recs, const uint64_t* group_start,
                             nv2++;
                         }
                         const uint64_t xstart = xcur;
+                        // CellPath order of this column's key type (cell_path.h)
+                        const bool key_signed = cpx_bit(cx.key_signed, x);
                         auto cmp_path = [&](uint64_t a, uint64_t b) -> int {
-                            return cmp_values(in.cpx.path_addr[a], in.cpx.path_len[a],
-                                              in.cpx.path_addr[b], in.cpx.path_len[b]);
+                            return cell_path_cmp((const uint8_t*)in.cpx.path_addr[a],
+                                                 in.cpx.path_len[a],
+                                                 (const uint8_t*)in.cpx.path_addr[b],
+                                                 in.cpx.path_len[b], key_signed);
                         };
                         while (true) {
                             int fi = -1;
@@ -3184,15 +3224,11 @@ __device__ inline void gc_cpx_move(UnfCols& u, uint64_t to, uint64_t from) {
     u.cpx.val_len[to] = u.cpx.val_len[from];
 }
 
-// CellPath order (BytesType map keys): unsigned lex, shorter-first on ties
-__device__ inline int gc_path_cmp(const UnfCols& a, uint64_t ae, const UnfCols& b, uint64_t be) {
-    const uint8_t* pa = (const uint8_t*)a.cpx.path_addr[ae];
-    const uint8_t* pb = (const uint8_t*)b.cpx.path_addr[be];
-    uint32_t la = a.cpx.path_len[ae], lb = b.cpx.path_len[be];
-    uint32_t n = la < lb ? la : lb;
-    for (uint32_t i = 0; i < n; i++)
-        if (pa[i] != pb[i]) return pa[i] < pb[i] ? -1 : 1;
-    return la == lb ? 0 : (la < lb ? -1 : 1);
+// CellPath order of the column's key type (cell_path.h)
+__device__ inline int gc_path_cmp(const UnfCols& a, uint64_t ae, const UnfCols& b, uint64_t be,
+                                  bool key_signed) {
+    return cell_path_cmp((const uint8_t*)a.cpx.path_addr[ae], a.cpx.path_len[ae],
+                         (const uint8_t*)b.cpx.path_addr[be], b.cpx.path_len[be], key_signed);
 }
 
 // per data partition: match to a source partition by decorated key, produce
@@ -3293,7 +3329,7 @@ __device__ inline bool gc_row_filter_active(UnfCols& out, uint64_t o, int64_t am
 // garbageFilterRow on the output arena row `o` vs tomb arena row `t`
 __device__ inline bool gc_filter_row_vs(UnfCols& out, uint64_t o, const UnfCols& tin, uint64_t t,
                                         int64_t am, uint32_t al, bool cell_level,
-                                        const SchemaParams& sch) {
+                                        const SchemaParams& sch, uint64_t cpx_key_signed) {
     int64_t tdm = (tin.flags[t] & PF_ROW_DEL) ? tin.rdel_mfda[t] : INT64_MIN;
     uint32_t tdl = (tin.flags[t] & PF_ROW_DEL) ? tin.rdel_ldt[t] : LDT_NONE_U32;
     int64_t dm = am;
@@ -3368,7 +3404,7 @@ __device__ inline bool gc_filter_row_vs(UnfCols& out, uint64_t o, const UnfCols&
             uint64_t xe = s0 + e;
             bool have_b = false;
             while (bi < tn) {
-                int pcmp = gc_path_cmp(tin, tb0 + bi, out, xe);
+                int pcmp = gc_path_cmp(tin, tb0 + bi, out, xe, cpx_bit(cpx_key_signed, x));
                 if (pcmp < 0) { bi++; continue; }
                 have_b = pcmp == 0;
                 break;
@@ -3437,7 +3473,8 @@ __device__ inline void gc_copy_unf(UnfCols& dst, uint64_t d, const UnfCols& src,
 
 __global__ void k_garbage_filter(OutParts dp, uint64_t nd, OutParts tp, UnfCols din,
                                  UnfCols tin, UnfCols dout, const int64_t* tomb_idx,
-                                 const uint64_t* new_base, SchemaParams sch, int cell_level) {
+                                 const uint64_t* new_base, SchemaParams sch, CpxTypes cx,
+                                 int cell_level) {
     uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= nd) return;
     uint64_t ob = new_base[g];
@@ -3568,7 +3605,8 @@ __global__ void k_garbage_filter(OutParts dp, uint64_t nd, OutParts tp, UnfCols 
             uint64_t t = tb + ti;
             if (din.rkind[d] == BK_CLUSTERING) {
                 gc_copy_unf(dout, slot, din, d, sch);
-                have = gc_filter_row_vs(dout, slot, tin, t, act_m, act_l, cell_level != 0, sch);
+                have = gc_filter_row_vs(dout, slot, tin, t, act_m, act_l, cell_level != 0, sch,
+                                        cx.key_signed);
             } else {
                 upd_open(tin, t, &tomb_open_m, &tomb_open_l);
                 act_m = pdm;

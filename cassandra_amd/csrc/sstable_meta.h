@@ -313,6 +313,103 @@ inline CkType ck_type(const std::string& t) {
     return {type_width(t), false};
 }
 
+// ---------------------------------------------------------------------------
+// collection and frozen column types. Type strings nest
+// (MapType(UTF8Type,FrozenType(MapType(A,B)))), so arguments are split at the
+// top-level commas only.
+// ---------------------------------------------------------------------------
+static const std::string MARSHAL_PFX = "org.apache.cassandra.db.marshal.";
+// t is MARSHAL_PFX + name + "(" + ...
+inline bool type_named(const std::string& t, const char* name) {
+    const std::string p = MARSHAL_PFX + name + "(";
+    return t.compare(0, p.size(), p) == 0;
+}
+// FrozenType(inner), any inner text: one opaque variable-width value, written
+// vint length + bytes and compared as bytes in the Cells.reconcile tie-break.
+// A simple column type for regular and static columns, never a clustering or
+// key type (ck_type and the key check know nothing of it). The header string
+// form org.apache.cassandra.db.marshal.FrozenType(inner) is recalled, not
+// checked against the Java sources.
+inline bool frozen_type(const std::string& t) {
+    return type_named(t, "FrozenType") && t.back() == ')';
+}
+// a multi-cell (complex) column type by its outer name. ListType counts, so
+// that a list sorts with the complex columns and its refusal names it.
+inline bool multicell_type(const std::string& t) {
+    return type_named(t, "MapType") || type_named(t, "SetType") || type_named(t, "ListType");
+}
+// what a regular or static SIMPLE column may be
+inline bool simple_column_type(const std::string& t) {
+    return simple_value_type(t) || frozen_type(t);
+}
+// The arguments of Name(arg,...), split at the top-level commas. Throws
+// std::runtime_error for text that is not Name(...) with balanced brackets.
+inline std::vector<std::string> type_args(const std::string& t) {
+    const size_t open = t.find('(');
+    if (open == std::string::npos || t.back() != ')')
+        throw std::runtime_error("unsupported column type " + t);
+    std::vector<std::string> args;
+    int depth = 0;
+    size_t start = open + 1;
+    for (size_t i = open + 1; i + 1 < t.size(); i++) {
+        const char c = t[i];
+        if (c == '(') depth++;
+        else if (c == ')') {
+            if (--depth < 0) throw std::runtime_error("unsupported column type " + t);
+        } else if (c == ',' && depth == 0) {
+            args.push_back(t.substr(start, i - start));
+            start = i + 1;
+        }
+    }
+    if (depth) throw std::runtime_error("unsupported column type " + t);
+    args.push_back(t.substr(start, t.size() - 1 - start));
+    return args;
+}
+// The collection types the engine merges: SetType(K) and MapType(K,V).
+//   K  BytesType, UTF8Type, AsciiType: cell paths compare as unsigned bytes
+//      (key_width 0); Int32Type (4), LongType (8), TimestampType (8): paths
+//      compare signed (cell_path.h) and must be exactly that wide.
+//   V  BytesType, UTF8Type, AsciiType or FrozenType(...): vint length + bytes.
+// Refused, as every one of them was before these types were accepted (same
+// exception type, so the same return code), with the full type string in the
+// message:
+//   a fixed-width V (Int32Type, LongType, TimestampType): the value would be
+//     written without its length prefix;
+//   ListType(...): its cell paths compare as TimeUUIDType;
+//   FrozenType(...) as K, any other K or V, nested multi-cell types;
+//   MapType(LongType,BytesType), the one combination of an accepted K and V
+//     held back: the suite that predates these types pins its refusal
+//     (multi_cpx_schema_test, header_union_test), and existing tests do not
+//     change with a feature. map<bigint,text>, map<timestamp,blob> and every
+//     other pairing are accepted.
+struct CollectionType {
+    bool is_set;
+    int32_t key_width;  // 0 = byte-ordered key, 4 / 8 = signed key of that width
+};
+inline CollectionType collection_type(const std::string& t) {
+    const std::string what = "unsupported column type " + t;
+    if (type_named(t, "ListType"))
+        throw std::runtime_error(what + " (list cells are ordered by TimeUUIDType paths, "
+                                        "which the engine does not compare)");
+    const bool is_set = type_named(t, "SetType");
+    if (!is_set && !type_named(t, "MapType")) throw std::runtime_error(what);
+    const std::vector<std::string> a = type_args(t);
+    if (a.size() != (is_set ? 1u : 2u)) throw std::runtime_error(what);
+    const std::string& k = a[0];
+    if (frozen_type(k) || !simple_value_type(k))
+        throw std::runtime_error(what + " (key type " + k + ")");
+    if (!is_set) {
+        const std::string& v = a[1];
+        if (type_width(v) > 0)
+            throw std::runtime_error(what + " (a fixed-width map value has no length prefix)");
+        if (!simple_column_type(v)) throw std::runtime_error(what + " (value type " + v + ")");
+    }
+    if (!is_set && k == MARSHAL_PFX + "LongType" && a[1] == MARSHAL_PFX + "BytesType")
+        throw std::runtime_error(what + " (map<bigint,blob> is held back; see collection_type)");
+    const int32_t w = type_width(k);
+    return {is_set, w > 0 ? w : 0};
+}
+
 struct HostSchema {
     std::vector<int32_t> col_fixed;     // SIMPLE regular columns only
     std::vector<int32_t> ck_widths;     // per clustering column
@@ -330,7 +427,26 @@ struct HostSchema {
         ck_desc.push_back(k.desc ? 1 : 0);
     }
     std::vector<int32_t> static_fixed;  // per static column
-    uint32_t n_cpx = 0;                 // trailing complex (map<blob,blob>) columns
+    uint32_t n_cpx = 0;                 // trailing complex (set / map) columns
+    // per complex column: the path width to enforce (0 = byte-ordered key, 4
+    // or 8 = signed key) and whether it is a set (cells carry no value)
+    std::vector<uint8_t> cpx_key_w, cpx_set;
+    void add_cpx(const CollectionType& c) {
+        n_cpx++;
+        cpx_key_w.push_back((uint8_t)c.key_width);
+        cpx_set.push_back(c.is_set ? 1 : 0);
+    }
+    // bit x == complex column x (at most 63): compares signed / is 8 bytes
+    // wide (not 4) / is a set
+    uint64_t cpx_mask(const std::vector<uint8_t>& v, uint8_t eq) const {
+        uint64_t m = 0;
+        for (size_t x = 0; x < v.size() && x < 64; x++)
+            if (eq ? v[x] == eq : v[x] != 0) m |= 1ull << x;
+        return m;
+    }
+    uint64_t cpx_key_signed_mask() const { return cpx_mask(cpx_key_w, 0); }
+    uint64_t cpx_key_w8_mask() const { return cpx_mask(cpx_key_w, 8); }
+    uint64_t cpx_is_set_mask() const { return cpx_mask(cpx_set, 0); }
     bool counters = false;              // counter table (every column CounterColumnType)
 };
 // The resolver of ONE header: rejects every layout the engine cannot walk.
@@ -347,25 +463,21 @@ inline HostSchema resolve_schema(const HStatistics& st) {
     for (auto& c : st.static_cols)
         if (reversed(c.second))
             throw unsupported_error("unsupported static column type " + c.second);
-    const std::string map_bb =
-        "org.apache.cassandra.db.marshal.MapType(org.apache.cassandra.db.marshal.BytesType,"
-        "org.apache.cassandra.db.marshal.BytesType)";
     for (size_t ci = 0; ci < rcols.size(); ci++) {
         const std::string& ct = rcols[ci].second;
         // the complex columns are the trailing run of the header's regular
         // columns (engine layout constraint: subset-bitmap bit n_simple + x
-        // is complex column x; the generator names its one 'zm' so name
-        // order puts it last)
-        if (hs.n_cpx && ct != map_bb)
+        // is complex column x; Columns order puts them last)
+        if (hs.n_cpx && !multicell_type(ct))
             throw std::runtime_error(
                 "complex columns must follow every simple regular column");
-        if (simple_value_type(ct)) hs.col_fixed.push_back(type_width(ct));
+        if (simple_column_type(ct)) hs.col_fixed.push_back(type_width(ct));
         else if (ct == "org.apache.cassandra.db.marshal.CounterColumnType") {
             hs.col_fixed.push_back(-1);
             hs.counters = true;
         }
-        else if (ct == map_bb) {
-            hs.n_cpx++;
+        else if (multicell_type(ct)) {
+            hs.add_cpx(collection_type(ct));  // throws for the refused ones
         } else {
             throw std::runtime_error("unsupported column type " + ct);
         }
@@ -386,7 +498,7 @@ inline HostSchema resolve_schema(const HStatistics& st) {
     }
     for (auto& t : st.clustering_types) hs.add_ck(t);
     for (auto& sc : st.static_cols) {
-        if (!simple_value_type(sc.second))
+        if (!simple_column_type(sc.second))
             throw std::runtime_error("unsupported static column type " + sc.second);
         hs.static_fixed.push_back(type_width(sc.second));
     }
@@ -422,8 +534,7 @@ inline std::string column_label(const bytes& name) {
 inline JobSchema resolve_job_schema(const std::vector<HStatistics>& stats, int k_data) {
     using Cols = std::vector<std::pair<bytes, std::string>>;
     if (k_data < 1 || (size_t)k_data > stats.size()) throw std::runtime_error("no compacting input");
-    const std::string map_prefix = "org.apache.cassandra.db.marshal.MapType(";
-    auto is_complex = [&](const std::string& t) { return t.compare(0, map_prefix.size(), map_prefix) == 0; };
+    auto is_complex = [&](const std::string& t) { return multicell_type(t); };
     for (size_t s = 1; s < stats.size(); s++) {
         if (stats[s].key_type != stats[0].key_type)
             throw unsupported_error("inputs differ in their partition key type: " +

@@ -40,6 +40,36 @@
  * strings in ck_types and checks the unfiltereds of each partition under that
  * comparator: ascending rows under a descending type are an error.
  *
+ * Collection columns. After its simple regular columns a table may have any
+ * number of complex columns (simple + complex <= 63) of the types
+ *   org.apache.cassandra.db.marshal.SetType(K)
+ *   org.apache.cassandra.db.marshal.MapType(K,V)
+ * K is BytesType, UTF8Type or AsciiType, whose cell paths order as unsigned
+ * bytes (shorter first), or Int32Type, LongType or TimestampType, whose paths
+ * order as Int32Type.compare / LongType.compareLongs do: the first byte
+ * signed, the rest unsigned, which for paths of one width is numeric order
+ * (TimestampType like LongType: recalled, as above). V is BytesType,
+ * UTF8Type, AsciiType or FrozenType(...) with any inner text: all written as
+ * vint length + bytes. A CellPath is vint length + bytes whatever K is. Type
+ * strings nest; MapType(K,V) is split at its top-level comma. In a column
+ * with int, bigint or timestamp keys a path that is not 4 resp. 8 bytes wide
+ * (an empty one included), and in a set column a cell that carries a value,
+ * is GPUC_ERR_FORMAT from compact, scrub and verify, never silently merged.
+ * FrozenType(...) with any inner text is also a simple column type of regular
+ * and static columns: variable width, sorted with the simple columns in
+ * Columns order, compared as bytes in the Cells.reconcile tie-break, never a
+ * clustering or key type. The header string form
+ * org.apache.cassandra.db.marshal.FrozenType(inner) is recalled, not checked
+ * against the Java sources. Still refused, with the full type string in the
+ * message and with the return code each had before the types above were
+ * accepted: a map with a fixed-width V (Int32Type, LongType, TimestampType:
+ * the value would lose its length prefix); ListType(...), whose paths compare
+ * as TimeUUIDType; FrozenType(...) as K, any other K or V, nested multi-cell
+ * types, MapType(LongType,BytesType) alone among the pairings of an accepted
+ * K and V (tests that predate these types pin its refusal; map<bigint,text>
+ * and map<timestamp,blob> are accepted), complex static columns, complex columns in counter tables, and a
+ * complex column before a simple one in the header.
+ *
  * The inputs of one job may list different columns in their serialization
  * headers (sstables older than an ALTER TABLE ... ADD, flushes that held only
  * some columns). Each input is parsed under its own header; the output header
@@ -502,7 +532,8 @@ typedef struct gpuc_flush_schema {
     uint32_t n_ck;
     const char* const* ck_types;
     uint32_t n_cols;            /* regular columns, header order; the complex
-                                 * (MapType) columns must be the LAST n_cpx */
+                                 * (SetType / MapType) columns must be the
+                                 * LAST n_cpx */
     const uint8_t* const* col_names;
     const uint32_t* col_name_lens;
     const char* const* col_types;
@@ -510,8 +541,15 @@ typedef struct gpuc_flush_schema {
     const uint8_t* const* static_names;
     const uint32_t* static_name_lens;
     const char* const* static_types;
-    uint32_t n_cpx;             /* number of trailing complex columns
-                                 * (map<blob,blob>; n_cols <= 63) */
+    uint32_t n_cpx;             /* number of trailing complex columns (n_cols
+                                 * <= 63). col_types takes the SetType(K) /
+                                 * MapType(K,V) strings of the top comment,
+                                 * and FrozenType(...) for a simple column.
+                                 * Checked per column, the message naming it:
+                                 * cells strictly ascending in the order of
+                                 * K, paths 4 / 8 bytes wide under int /
+                                 * bigint, timestamp keys, no value in a
+                                 * set's cells */
     uint32_t column_index_size; /* 0 = 64 KiB */
     uint32_t snappy;            /* chunk codec for the output */
     uint32_t bti;               /* write the `da` (trie-indexed) components */
