@@ -21,6 +21,7 @@
 #include <set>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -60,35 +61,40 @@ static PinnedSlot g_pin_in[2][64], g_pin_out[2][4];
 
 // GPUC_TRACE=1: wall-clock checkpoints on stderr (host-gap hunting)
 static bool g_trace = getenv("GPUC_TRACE") != nullptr;
-// validation mode: set by gpuc_validate around its gpuc_compact-shaped run
-static thread_local const char* g_validate_out = nullptr;
-static thread_local uint64_t g_validate_count = 0;
-// Merkle-leaf validation: set by gpuc_validate_merkle around its run, in place
-// of g_validate_out. The spec is checked before it gets here.
+// Merkle-leaf validation (gpuc_validate_merkle). The spec is checked before it
+// gets here.
 struct MerkleRun {
     const gpuc_merkle_spec* spec;
     uint8_t* leaf_hash;         // n_leaves * 32, out
     uint64_t* leaf_partitions;  // n_leaves, out; may be NULL
     uint64_t n_partitions;      // out: sum of the leaf counts
 };
-static thread_local MerkleRun* g_merkle = nullptr;
-// Routed outputs: set by gpuc_compact_routed around its run. The spec is
-// checked before it gets here.
+// Routed outputs (gpuc_compact_routed). The spec is checked before it gets here.
 struct RouteRun {
     const gpuc_route_spec* spec;
     gpuc_route_output* outputs;  // n_outputs, out; may be NULL
 };
-static thread_local RouteRun* g_route = nullptr;
+// What a run of run_compaction produces: at most one member is set, and with
+// none set it writes sstable(s). Each entry point fills it in and passes it
+// down by reference, shard workers included; the entry points' argument
+// checks decide which job options a mode may be combined with.
+struct CompactMode {
+    const char* digest_path = nullptr;  // gpuc_validate: the digest file
+    uint64_t* digest_count = nullptr;   //   out: partitions digested
+    MerkleRun* merkle = nullptr;
+    RouteRun* route = nullptr;
+};
 static double g_trace_t0 = 0;
-static double trace_wall() {
+static double wall_ms() {
     struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts);
     return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
 }
 static void TR(const char* tag) {
     if (!g_trace) return;
-    double t = trace_wall();
+    double t = wall_ms();
     fprintf(stderr, "[gpuc %8.1f] %s\n", t - g_trace_t0, tag);
 }
+static bool file_exists(const std::string& path) { return access(path.c_str(), F_OK) == 0; }
 
 
 // threaded read of a whole file into (pinned) memory
@@ -201,6 +207,14 @@ struct DevBuf {
     ~DevBuf() { free_(); }
     template <typename T> T* as() const { return (T*)p; }
 };
+// Allocate n elements (+ pad bytes) and copy them up asynchronously: `src`
+// must outlive the next synchronise of `stream`.
+template <typename T>
+static T* upload(DevBuf& d, const T* src, size_t n, hipStream_t stream, size_t pad = 0) {
+    d.alloc(n * sizeof(T) + pad);
+    if (n) HIP_CHECK(hipMemcpyAsync(d.p, src, n * sizeof(T), hipMemcpyHostToDevice, stream));
+    return d.as<T>();
+}
 
 // exclusive scan over u64; returns total
 static uint64_t exscan_u64(uint64_t* d_data, uint64_t n, hipStream_t stream) {
@@ -279,9 +293,7 @@ static MRec* merge_sorted_runs(MRec* d_a, MRec* d_b, std::vector<uint64_t> runs 
             next_runs.push_back(p.b_end);
         }
         DevBuf d_pairs;
-        d_pairs.alloc(pairs.size() * sizeof(MergePair));
-        HIP_CHECK(hipMemcpyAsync(d_pairs.p, pairs.data(), pairs.size() * sizeof(MergePair),
-                                 hipMemcpyHostToDevice, stream));
+        upload(d_pairs, pairs.data(), pairs.size(), stream);
         uint64_t total_tiles = tile_beg;
         hipLaunchKernelGGL(k_merge_pairs, dim3((uint32_t)((total_tiles + 255) / 256)), dim3(256), 0,
                            stream, in, out, d_pairs.as<MergePair>(), (uint32_t)pairs.size(), total_tiles, lut);
@@ -442,6 +454,20 @@ struct WriteDeviceOut {
     uint64_t partitions = 0, rows = 0, cells = 0;
     double ms_sizes = 0, ms_serialize = 0, ms_compress = 0, ms_d2h = 0, ms_io = 0;
     uint32_t n_outputs = 1;  // sstables written (more than one only when size-split)
+    // totals over several writer runs (routed outputs); start from n_outputs = 0
+    void add(const WriteDeviceOut& o) {
+        n_outputs += o.n_outputs;
+        partitions += o.partitions;
+        rows += o.rows;
+        cells += o.cells;
+        uncompressed_len += o.uncompressed_len;
+        compressed_len += o.compressed_len;
+        ms_sizes += o.ms_sizes;
+        ms_serialize += o.ms_serialize;
+        ms_compress += o.ms_compress;
+        ms_d2h += o.ms_d2h;
+        ms_io += o.ms_io;
+    }
 };
 
 // The one place chunk-compress kernels are launched (sstable writer and
@@ -543,13 +569,10 @@ struct DecodedFile {
     std::vector<ChunkDesc> h_chunks;
     void issue(const HCompressionInfo& ci, const std::vector<ChunkFrame>& frames,
                const bytes& file, const DevBuf& d_error, uint8_t* d_bad, hipStream_t stream) {
-        comp.alloc(file.size());
-        HIP_CHECK(hipMemcpyAsync(comp.p, file.data(), file.size(), hipMemcpyHostToDevice, stream));
+        upload(comp, file.data(), file.size(), stream);
         data.alloc(ci.data_len + 16);
         h_chunks = chunk_descs(frames, comp.as<uint8_t>(), 0, data.as<uint8_t>(), ci.chunk_len);
-        chunks.alloc(h_chunks.size() * sizeof(ChunkDesc) + 16);
-        HIP_CHECK(hipMemcpyAsync(chunks.p, h_chunks.data(), h_chunks.size() * sizeof(ChunkDesc),
-                                 hipMemcpyHostToDevice, stream));
+        upload(chunks, h_chunks.data(), h_chunks.size(), stream, 16);
         launch_chunk_decompress(ci, chunks, h_chunks.size(), d_error, d_bad, stream);
     }
 };
@@ -561,10 +584,7 @@ struct DevSchema {
     SchemaParams upload(const HostSchema& hs, hipStream_t stream,
                         uint32_t column_index_size = 64 * 1024) {
         auto up = [&](DevBuf& d, const std::vector<int32_t>& h) {
-            d.alloc(h.size() * 4 + 8);
-            if (!h.empty())
-                HIP_CHECK(hipMemcpyAsync(d.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, stream));
-            return d.as<int32_t>();
+            return gpuc::upload(d, h.data(), h.size(), stream, 8);
         };
         SchemaParams sch{};
         sch.n_ck = (uint32_t)hs.ck_widths.size();
@@ -1667,7 +1687,7 @@ static void set_err(char* dst, size_t cap, const std::string& msg) {
     snprintf(dst, cap, "%s", msg.c_str());
 }
 // The exception-to-code ladder of the entry points that report through an
-// error buffer. gpuc_compact (cancellation, timing), gpuc_verify and
+// error buffer. run_compaction (cancellation, timing), gpuc_verify and
 // gpuc_compress_buffer map differently and spell their own.
 template <class F> static int abi_guard(char* err, size_t cap, F&& body) {
     try {
@@ -1692,7 +1712,6 @@ struct CompactSetup {
     std::vector<HCompressionInfo> cinfos;
     uint32_t out_chunk_len = CHUNK_LEN;  // resolved from the job / cinfos[0]
     std::vector<HStatistics> stats;
-    std::vector<uint64_t> generations;
     std::vector<std::vector<uint64_t>> positions;   // n_parts+1 absolute offsets
     std::vector<std::vector<uint64_t>> entry_offs;  // Index.db entry byte offsets
     std::vector<std::vector<bti::bytes>> bti_prefixes;  // da: trie separator per partition
@@ -1723,11 +1742,6 @@ struct CompactSetup {
     }
 };
 
-// Everything from data read through component write for ONE output sstable,
-// restricted to the partition window pr[s] = [blo, bhi) per input (the full
-// range in the unsharded case). wslot selects the pinned-arena set; shards
-// run two at a time so front-phase kernels of one shard overlap the other
-// shard's LDS-bound compress (they use disjoint CU resources).
 struct cancelled_error : std::runtime_error {
     cancelled_error() : std::runtime_error("compaction cancelled (cancel_flag set)") {}
 };
@@ -1756,13 +1770,9 @@ struct ValidateNames {
             names.insert(names.end(), nm.begin(), nm.end());
         }
         noff.push_back((uint32_t)names.size());
-        d_names.alloc(names.size() + 8);
-        d_noff.alloc(noff.size() * 4);
-        HIP_CHECK(hipMemcpyAsync(d_names.p, names.data(), names.size(), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipMemcpyAsync(d_noff.p, noff.data(), noff.size() * 4, hipMemcpyHostToDevice, stream));
         ValidateParams vpar{};
-        vpar.names = d_names.as<uint8_t>();
-        vpar.name_off = d_noff.as<uint32_t>();
+        vpar.names = gpuc::upload(d_names, names.data(), names.size(), stream, 8);
+        vpar.name_off = gpuc::upload(d_noff, noff.data(), noff.size(), stream);
         vpar.n_reg = (uint32_t)header.regular_cols.size();
         vpar.n_static = (uint32_t)header.static_cols.size();
         vpar.counters = sch.counters;
@@ -1773,79 +1783,113 @@ struct ValidateNames {
     }
 };
 
-static void compact_one(const gpuc_job* job, const CompactSetup& su,
-                        const std::vector<std::pair<uint32_t, uint32_t>>& pr,
-                        const std::string& out_base_str, int wslot,
-                        gpuc_result* res, std::mutex& res_mu,
-                        bool shard_exact = false, int64_t sh_lo = 0, int64_t sh_hi = 0) {
-    auto wall = []() {
-        struct timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
-    };
-    HIP_CHECK(hipSetDevice(job->device));
-    Stream stream;
-    {
-        int k = su.k;
-        const auto& in_bases = su.in_bases;
-        const auto& cinfos = su.cinfos;
-        const auto& stats = su.stats;
-        const auto& generations = su.generations;
-        const auto& positions = su.positions;
+// k_validate_digest over the reconciled groups (Validator.rowHash): 32 bytes
+// per group into d_hash. Both validation epilogues launch it here.
+static void launch_validate_digest(const OutParts& op, const UnfColsBuf& rows, uint64_t n_groups,
+                                   const ValidateParams& vpar, DevBuf& d_hash,
+                                   hipStream_t stream) {
+    d_hash.alloc(n_groups * 32 + 32);
+    if (!n_groups) return;
+    hipLaunchKernelGGL(k_validate_digest, dim3((uint32_t)((n_groups + 255) / 256)), dim3(256), 0,
+                       stream, op, rows.uc, n_groups, vpar, d_hash.as<uint8_t>());
+}
 
-        double t0 = wall();
-        // per-input window: partition range -> chunk range -> compressed range
-        std::vector<uint32_t> win_blo(k), win_n(k);
-        std::vector<ChunkWindow> win(k);
-        std::vector<uint64_t> win_comp_lo(k);
-        std::vector<size_t> comp_sz(k, 0);        // compressed bytes in window
-        std::vector<uint8_t*> comp_pin(k, nullptr);
+// ---------------------------------------------------------------------------
+// The stages of compact_one. Each struct owns its device buffers AND the host
+// staging that its async copies read. compact_one declares them in its own
+// scope, after its Stream, so all of it outlives every synchronise of the run
+// and is released before the stream is destroyed.
+// ---------------------------------------------------------------------------
+
+// What one compact_one call covers and where its output goes: the partition
+// window pr[s] = [blo, bhi) per input (the full range in the unsharded case),
+// the output base and the pinned-arena set. Shards run two at a time so
+// front-phase kernels of one shard overlap the other shard's LDS-bound
+// compress (they use disjoint CU resources).
+struct ShardWindow {
+    std::vector<std::pair<uint32_t, uint32_t>> pr;
+    std::string out_base;
+    int wslot = 0;
+    // da internal shards: trie-separator windows are one partition wide of
+    // exact; this token filter (on GPU-computed tokens) is the exact boundary
+    bool exact = false;
+    int64_t tok_lo = 0, tok_hi = 0;
+};
+
+// Window ingest: partition window -> chunk range -> compressed range per
+// input, the Data.db bytes (own reader threads, or the stripes compact_setup
+// pre-read), H2D on the copy stream and the per-source decompress on the main
+// stream, which waits on ev_h2d[s] first. Synchronises nothing: the caller
+// reads d_error next. The merge compares keys inside the decompressed bytes
+// and the writer copies values out of them, so this lives for the whole run.
+struct WindowIngest {
+    std::vector<uint32_t> win_blo, win_n;
+    std::vector<ChunkWindow> win;
+    std::vector<uint64_t> win_comp_lo;
+    std::vector<size_t> comp_sz;  // compressed bytes in window
+    std::vector<uint8_t*> comp_pin;
+    bool adopt = false;           // setup pre-read the whole files
+    std::vector<std::thread> readers;
+    std::optional<Stream> copy_stream;  // created by issue(); ahead of its buffers
+    std::vector<DevBuf> d_comp, d_data, d_pos, d_chunks;
+    std::vector<std::vector<ChunkDesc>> chunks;
+    std::vector<Event> ev_h2d;          // one per input: its uploads are done
+    std::vector<const uint8_t*> vbase;  // virtual decompressed origin
+    ~WindowIngest() {
+        // an error between resolve() and issue() must not leave a reader running
+        for (auto& t : readers)
+            if (t.joinable()) t.join();
+    }
+    // windows, pinned arenas, and the reads started
+    void resolve(const CompactSetup& su, const ShardWindow& sw) {
+        const int k = su.k;
+        win_blo.resize(k);
+        win_n.resize(k);
+        win.resize(k);
+        win_comp_lo.resize(k);
+        comp_sz.assign(k, 0);
+        comp_pin.assign(k, nullptr);
         for (int s = 0; s < k; s++) {
-            win_blo[s] = pr[s].first;
-            win_n[s] = pr[s].second - pr[s].first;
-            win[s] = chunk_window(cinfos[s], su.comp_file_sz[s], positions[s], pr[s].first,
-                                  pr[s].second);
+            win_blo[s] = sw.pr[s].first;
+            win_n[s] = sw.pr[s].second - sw.pr[s].first;
+            win[s] = chunk_window(su.cinfos[s], su.comp_file_sz[s], su.positions[s],
+                                  sw.pr[s].first, sw.pr[s].second);
             win_comp_lo[s] = win[s].comp_lo;
             comp_sz[s] = win[s].comp_hi - win[s].comp_lo;
         }
-        bool adopt = !su.full_pin.empty();
-        std::vector<std::thread> data_readers(adopt ? 0 : k);
+        adopt = !su.full_pin.empty();
+        readers.resize(adopt ? 0 : k);
         for (int s = 0; s < k; s++) {
             if (adopt) {
                 // setup already reads the whole file into the slot-0 arenas
                 comp_pin[s] = su.full_pin[s] + win_comp_lo[s];
             } else {
-                comp_pin[s] = (uint8_t*)g_pin_in[wslot][s].get(comp_sz[s] ? comp_sz[s] : 1);
+                comp_pin[s] = (uint8_t*)g_pin_in[sw.wslot][s].get(comp_sz[s] ? comp_sz[s] : 1);
                 if (!comp_pin[s]) throw std::runtime_error("pinned alloc failed");
-                data_readers[s] = std::thread([&, s] {
+                readers[s] = std::thread([this, &su, s] {
                     if (comp_sz[s])
-                        read_file_range(in_bases[s] + "-Data.db", comp_pin[s], win_comp_lo[s],
+                        read_file_range(su.in_bases[s] + "-Data.db", comp_pin[s], win_comp_lo[s],
                                         comp_sz[s], 3);
                 });
             }
         }
-        {
-            std::lock_guard<std::mutex> g(res_mu);
-            res->ms_read_io += wall() - t0;
-        }
-        TR("window resolved");
-        check_cancel(job);
-
-        // ---- H2D + decompress (pipelined per sstable) ----
-        Stream copy_stream;
-        Event e0, e1, e2, e3, e4, er0, er1;
-        HIP_CHECK(hipEventRecord(e0, stream));
-        std::vector<DevBuf> d_comp(k), d_data(k), d_pos(k), d_chunks_s(k);
-        DevBuf d_error;
-        d_error.alloc(8);
-        HIP_CHECK(hipMemsetAsync(d_error.p, 0, 8, stream));
-        std::vector<Event> ev_h2d(k);  // one per input: its uploads are done
-        std::vector<std::vector<ChunkDesc>> chunks_all(k);  // kept alive past async copies
+    }
+    // H2D + decompress, pipelined per sstable. Returns the residual read wait
+    // (ms) that the pipeline did not hide.
+    double issue(const CompactSetup& su, const DevBuf& d_error, hipStream_t stream) {
+        const int k = su.k;
+        copy_stream.emplace();
+        d_comp = std::vector<DevBuf>(k);
+        d_data = std::vector<DevBuf>(k);
+        d_pos = std::vector<DevBuf>(k);
+        d_chunks = std::vector<DevBuf>(k);
+        ev_h2d = std::vector<Event>(k);
+        chunks.resize(k);
+        vbase.assign(k, nullptr);
         double ms_read_data = 0;
-        std::vector<const uint8_t*> vbase(k, nullptr);  // virtual decompressed origin
         for (int s = 0; s < k; s++) {
-            double tr = wall();
-            auto& ci = cinfos[s];
+            double tr = wall_ms();
+            auto& ci = su.cinfos[s];
             const uint64_t icl = ci.chunk_len;  // inputs of one job may differ
             const uint64_t c_lo = win[s].c_lo, n_wchunks = win[s].c_hi - c_lo;
             d_comp[s].alloc(comp_sz[s] ? comp_sz[s] : 1);
@@ -1858,7 +1902,7 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                     if (sr.len[t])
                         HIP_CHECK(hipMemcpyAsync(d_comp[s].as<uint8_t>() + sr.off[t],
                                                  comp_pin[s] + sr.off[t], sr.len[t],
-                                                 hipMemcpyHostToDevice, copy_stream));
+                                                 hipMemcpyHostToDevice, *copy_stream));
                 }
             } else if (adopt) {
                 // token-restricted window over a preread file: wait for all
@@ -1868,152 +1912,76 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
                     if (t.valid()) t.wait();
                 if (comp_sz[s])
                     HIP_CHECK(hipMemcpyAsync(d_comp[s].p, comp_pin[s], comp_sz[s],
-                                             hipMemcpyHostToDevice, copy_stream));
+                                             hipMemcpyHostToDevice, *copy_stream));
             } else {
-                data_readers[s].join();  // in-order wait; all reads run concurrently
+                readers[s].join();  // in-order wait; all reads run concurrently
                 if (comp_sz[s])
                     HIP_CHECK(hipMemcpyAsync(d_comp[s].p, comp_pin[s], comp_sz[s],
-                                             hipMemcpyHostToDevice, copy_stream));
+                                             hipMemcpyHostToDevice, *copy_stream));
             }
-            ms_read_data = wall() - tr + ms_read_data;
+            ms_read_data = wall_ms() - tr + ms_read_data;
             d_data[s].alloc(n_wchunks * icl + 16);
             // positions stay ABSOLUTE: the decompressed window is addressed
             // through a virtual origin so partition offsets need no rewrite
             vbase[s] = d_data[s].as<uint8_t>() - c_lo * icl;
-            uint64_t n_wpos = (uint64_t)win_n[s] + 1;
-            d_pos[s].alloc(n_wpos * 8);
-            HIP_CHECK(hipMemcpyAsync(d_pos[s].p, positions[s].data() + win_blo[s], n_wpos * 8,
-                                     hipMemcpyHostToDevice, copy_stream));
-            auto& chunks = chunks_all[s];
-            chunks = chunk_descs(chunk_frames(ci, su.comp_file_sz[s], c_lo, win[s].c_hi),
-                                 d_comp[s].as<uint8_t>(), win_comp_lo[s],
-                                 d_data[s].as<uint8_t>(), ci.chunk_len);
-            d_chunks_s[s].alloc(chunks.size() * sizeof(ChunkDesc) + 16);
-            if (!chunks.empty())
-                HIP_CHECK(hipMemcpyAsync(d_chunks_s[s].p, chunks.data(), chunks.size() * sizeof(ChunkDesc),
-                                         hipMemcpyHostToDevice, copy_stream));
-            HIP_CHECK(hipEventRecord(ev_h2d[s], copy_stream));
+            upload(d_pos[s], su.positions[s].data() + win_blo[s], (size_t)win_n[s] + 1,
+                   *copy_stream);
+            chunks[s] = chunk_descs(chunk_frames(ci, su.comp_file_sz[s], c_lo, win[s].c_hi),
+                                    d_comp[s].as<uint8_t>(), win_comp_lo[s],
+                                    d_data[s].as<uint8_t>(), ci.chunk_len);
+            upload(d_chunks[s], chunks[s].data(), chunks[s].size(), *copy_stream, 16);
+            HIP_CHECK(hipEventRecord(ev_h2d[s], *copy_stream));
             HIP_CHECK(hipStreamWaitEvent(stream, ev_h2d[s], 0));
-            launch_chunk_decompress(ci, d_chunks_s[s], chunks.size(), d_error, nullptr, stream);
+            launch_chunk_decompress(ci, d_chunks[s], chunks[s].size(), d_error, nullptr, stream);
         }
-        {
-            std::lock_guard<std::mutex> g(res_mu);
-            res->ms_read_io += ms_read_data;  // residual read wait not hidden by the pipeline
-        }
-        TR("ingest issued");
-        HIP_CHECK(hipEventRecord(e1, stream));  // e0..e1: H2D+decompress pipeline (overlapped)
-        HIP_CHECK(hipEventRecord(e2, stream));
-
-        // corrupt inputs must fail cleanly, not fault the GPU: the parse
-        // walk trusts decompressed bytes, so the chunk-CRC verdict is checked
-        // BEFORE any parse kernel touches them
-        if (unsigned long long err = read_dev_error(d_error, stream))
-            throw std::runtime_error("input chunk decompress/CRC failed, code " +
-                                     std::to_string(err));
-
-        // ---- parse (pass A: count + partition meta; pass B: row decode) ----
+        return ms_read_data;
+    }
+    // the parse's source descriptors over the window; returns total partitions
+    uint64_t source_descs(const CompactSetup& su, std::vector<SrcDesc2>& srcs) const {
         uint64_t total_parts = 0;
-        std::vector<SrcDesc2> srcs(k);
-        for (int s = 0; s < k; s++) {
+        srcs.resize(su.k);
+        for (int s = 0; s < su.k; s++) {
             srcs[s].data = vbase[s];
             srcs[s].part_pos = d_pos[s].as<uint64_t>();
             srcs[s].n_parts = win_n[s];
-            srcs[s].min_ts = stats[s].hdr_min_ts;
-            srcs[s].min_ldt = stats[s].hdr_min_ldt;
-            srcs[s].min_ttl = stats[s].hdr_min_ttl;
+            srcs[s].min_ts = su.stats[s].hdr_min_ts;
+            srcs[s].min_ldt = su.stats[s].hdr_min_ldt;
+            srcs[s].min_ttl = su.stats[s].hdr_min_ttl;
             srcs[s].rec_base = (uint32_t)total_parts;
             set_src_columns(srcs[s], su.js.src[s]);
             total_parts += srcs[s].n_parts;
         }
         if (total_parts > 0xFFFFFFFFull) throw std::runtime_error("too many partitions for one job");
-        DevSchema dsch;
-        SchemaParams sch = dsch.upload(su.js.schema, stream);
-        DevBuf d_srcs, d_recs_a, d_recs_b, d_rows_in;
-        d_srcs.alloc(srcs.size() * sizeof(SrcDesc2));
-        HIP_CHECK(hipMemcpyAsync(d_srcs.p, srcs.data(), srcs.size() * sizeof(SrcDesc2),
-                                 hipMemcpyHostToDevice, stream));
-        d_recs_a.alloc(total_parts * sizeof(MRec));
-        d_recs_b.alloc(total_parts * sizeof(MRec));
-        d_rows_in.alloc(8);
-        HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
-        ParsedInput parsed;
-        parsed.cx = cpx_types(su.js.schema);
-        parse_input(parsed, d_srcs, (uint32_t)k, total_parts, d_recs_a, sch, d_error, d_rows_in,
-                    false, stream);
-        const ParsedCols& pc = parsed.pc;
-        const uint64_t total_in_cpx = parsed.total_cpx;
-        HIP_CHECK(hipEventRecord(e3, stream));
-        {
-            unsigned long long err = read_dev_error(d_error, stream);
-            TR("parse synced");
-            check_cancel(job);  // a set cancel flag takes precedence over a parse error
-            throw_if_collection_parse_error(err);
-            if (err) throw std::runtime_error("GPU decode/parse error code " + std::to_string(err));
-            uint64_t rows_in_local = 0;
-            HIP_CHECK(hipMemcpy(&rows_in_local, d_rows_in.p, 8, hipMemcpyDeviceToHost));
-            std::lock_guard<std::mutex> g(res_mu);
-            res->rows_in += rows_in_local;
-        }
-
-        // exact-key comparator fallback: point the merge kernels at the
-        // decompressed inputs (keys > 8 bytes tie-break by byte walk)
+        return total_parts;
+    }
+    // exact-key comparator fallback: point the merge kernels at the
+    // decompressed inputs (keys > 8 bytes tie-break by byte walk)
+    KeyLut key_lut() const {
         KeyLut lut{};
-        for (int s2 = 0; s2 < k; s2++) {
-            lut.base[s2] = vbase[s2];
-            lut.pos[s2] = d_pos[s2].as<uint64_t>();
+        for (size_t s = 0; s < vbase.size(); s++) {
+            lut.base[s] = vbase[s];
+            lut.pos[s] = d_pos[s].as<uint64_t>();
         }
         lut.enabled = 1;
+        return lut;
+    }
+};
 
-        // ---- merge (pairwise rounds over pre-sorted source runs) ----
-        // In garbage-collect mode the first k_data inputs are the compacted
-        // data; the rest are tombstone sources merged in a second pass.
-        int kd = su.k_data > 0 ? su.k_data : k;
-        bool gc_mode = kd < k;
-        uint64_t data_parts = 0;
-        for (int s = 0; s < kd; s++) data_parts += srcs[s].n_parts;
-        std::vector<uint64_t> runs;
-        runs.push_back(0);
-        for (int s = 0; s < kd; s++) runs.push_back(runs.back() + srcs[s].n_parts);
-        MRec* d_sorted = merge_sorted_runs(d_recs_a.as<MRec>(), d_recs_b.as<MRec>(), runs, stream, lut);
-        TR("merge issued");
+// the event pairs behind gpuc_result's phase times, all on the main stream
+struct PhaseEvents {
+    Event e0, e1, e2, e3, e4, er0, er1;
+};
 
-        // ---- group heads + starts ----
-        Groups groups;
-        find_groups(groups, d_sorted, data_parts, lut, stream);
-        const uint64_t n_groups = groups.n;
-        TR("groups known");
-        check_cancel(job);
-
-        // ---- reconcile + purge ----
-        // Host staging for the small async H2D setup copies below. These must
-        // outlive the copies until the next hipStreamSynchronize on `stream`
-        // (an async copy from freed pageable memory is undefined), so they
-        // live at this scope, past the reconcile-phase sync.
-        std::vector<uint32_t> bases(k);
-        std::vector<int64_t> klo_h, khi_h, ov_lo_h, ov_hi_h, ov_ts_h;
-        DevBuf d_srcbases;
-        {
-            for (int s = 0; s < k; s++) bases[s] = srcs[s].rec_base;
-            d_srcbases.alloc(k * 4);
-            HIP_CHECK(hipMemcpyAsync(d_srcbases.p, bases.data(), k * 4, hipMemcpyHostToDevice, stream));
-        }
-        scan_group_rows(groups, d_srcbases, pc, stream);
-        TR("out rows scanned");
-        Reconciled rec;
-        rec.alloc(groups, sch, total_in_cpx, stream);
-        OutPartsBuf& opb = rec.parts;
-        UnfColsBuf& out_rows = rec.rows;
-        DevBuf& d_stats = rec.stats;
-        DevBuf d_tomb, d_ctr_arena;
-        uint64_t ctr_arena_cap = 0;
-        if (sch.counters) {
-            ctr_arena_cap = counter_arena_cap(parsed, sch.n_cols, stream);
-            d_ctr_arena.alloc(ctr_arena_cap);
-            sch.ctr_arena = d_ctr_arena.as<uint8_t>();
-        }
-        uint32_t tomb_cap = tomb_list_cap(groups.total_rows, total_in_cpx, n_groups, sch);
-        d_tomb.alloc((uint64_t)tomb_cap * 4);
-        DevBuf d_ov_lo, d_ov_hi, d_ov_ts;
+// Purge inputs: the job's purge options, keep ranges, overlaps (with their
+// bloom bit arrays packed into one buffer) and the shard's exact token bounds
+// as a PurgeParams2. The async copies read the host vectors here.
+struct PurgeInputs {
+    std::vector<int64_t> klo, khi, ov_lo, ov_hi, ov_ts;
+    std::vector<uint32_t> ov_bw;
+    std::vector<uint64_t> ov_boff, ov_bbits;
+    std::vector<int32_t> ov_bk;
+    DevBuf d_kr_lo, d_kr_hi, d_ov_lo, d_ov_hi, d_ov_ts, d_ov_bw, d_ov_boff, d_ov_bbits, d_ov_bk;
+    PurgeParams2 build(const gpuc_job* job, const ShardWindow& sw, hipStream_t stream) {
         PurgeParams2 pp{};
         pp.now_sec = job->now_sec;
         pp.gc_before = job->gc_before;
@@ -2023,417 +1991,513 @@ static void compact_one(const gpuc_job* job, const CompactSetup& su,
         pp.has_shard = job->has_token_range;
         pp.shard_lo = job->token_lo;
         pp.shard_hi = job->token_hi;
-        if (shard_exact) {
-            // da internal shards: trie-separator windows are one partition
-            // wide of exact; this token filter (on GPU-computed tokens) is
-            // the exact boundary, intersected with any job-level range
+        if (sw.exact) {
+            // intersected with any job-level range
             if (pp.has_shard) {
-                pp.shard_lo = std::max(pp.shard_lo, sh_lo);
-                pp.shard_hi = std::min(pp.shard_hi, sh_hi);
+                pp.shard_lo = std::max(pp.shard_lo, sw.tok_lo);
+                pp.shard_hi = std::min(pp.shard_hi, sw.tok_hi);
             } else {
                 pp.has_shard = 1;
-                pp.shard_lo = sh_lo;
-                pp.shard_hi = sh_hi;
+                pp.shard_lo = sw.tok_lo;
+                pp.shard_hi = sw.tok_hi;
             }
         }
-        DevBuf d_kr_lo, d_kr_hi;
         if (job->n_keep_ranges > 0) {
-            klo_h.resize(job->n_keep_ranges);
-            khi_h.resize(job->n_keep_ranges);
             for (int i = 0; i < job->n_keep_ranges; i++) {
-                klo_h[i] = job->keep_ranges[i].token_lo;
-                khi_h[i] = job->keep_ranges[i].token_hi;
+                klo.push_back(job->keep_ranges[i].token_lo);
+                khi.push_back(job->keep_ranges[i].token_hi);
             }
-            d_kr_lo.alloc(job->n_keep_ranges * 8);
-            d_kr_hi.alloc(job->n_keep_ranges * 8);
-            HIP_CHECK(hipMemcpyAsync(d_kr_lo.p, klo_h.data(), job->n_keep_ranges * 8, hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(d_kr_hi.p, khi_h.data(), job->n_keep_ranges * 8, hipMemcpyHostToDevice, stream));
-            pp.kr_lo = d_kr_lo.as<int64_t>();
-            pp.kr_hi = d_kr_hi.as<int64_t>();
+            pp.kr_lo = upload(d_kr_lo, klo.data(), klo.size(), stream);
+            pp.kr_hi = upload(d_kr_hi, khi.data(), khi.size(), stream);
             pp.n_keep_ranges = job->n_keep_ranges;
             pp.invert_ranges = job->invert_ranges;
         }
-        // Merkle-leaf validation: assign every group its leaf now, so that
-        // reconcile drops the partitions of no tree before merging them
-        DevBuf d_mk_left, d_mk_begin, d_mk_right, d_group_leaf;
-        uint32_t mk_leaves = 0;
-        if (g_merkle) {
-            const gpuc_merkle_spec& ms = *g_merkle->spec;
-            mk_leaves = ms.leaf_begin[ms.n_trees];
-            d_mk_left.alloc((uint64_t)ms.n_trees * 8);
-            d_mk_begin.alloc(((uint64_t)ms.n_trees + 1) * 4);
-            d_mk_right.alloc((uint64_t)mk_leaves * 8);
-            d_group_leaf.alloc(n_groups * 4 + 4);
-            HIP_CHECK(hipMemcpyAsync(d_mk_left.p, ms.tree_left, (uint64_t)ms.n_trees * 8, hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(d_mk_begin.p, ms.leaf_begin, ((uint64_t)ms.n_trees + 1) * 4, hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(d_mk_right.p, ms.leaf_right, (uint64_t)mk_leaves * 8, hipMemcpyHostToDevice, stream));
-            MerkleParams mp{d_mk_left.as<int64_t>(), d_mk_begin.as<uint32_t>(),
-                            d_mk_right.as<int64_t>(), ms.n_trees};
-            if (n_groups)
-                hipLaunchKernelGGL(k_merkle_assign, dim3((uint32_t)((n_groups + 255) / 256)),
-                                   dim3(256), 0, stream, groups.sorted,
-                                   groups.start.as<uint64_t>(), n_groups, mp,
-                                   d_group_leaf.as<int32_t>());
-            pp.group_leaf = d_group_leaf.as<int32_t>();
-        }
-        DevBuf d_ov_bw, d_ov_boff, d_ov_bbits, d_ov_bk;
-        std::vector<uint32_t> ov_bw_h;
-        std::vector<uint64_t> ov_boff_h, ov_bbits_h;
-        std::vector<int32_t> ov_bk_h;
         if (job->n_overlaps > 0) {
-            ov_lo_h.resize(job->n_overlaps);
-            ov_hi_h.resize(job->n_overlaps);
-            ov_ts_h.resize(job->n_overlaps);
             bool any_bloom = false;
             for (int i = 0; i < job->n_overlaps; i++) {
-                ov_lo_h[i] = job->overlaps[i].token_lo;
-                ov_hi_h[i] = job->overlaps[i].token_hi;
-                ov_ts_h[i] = job->overlaps[i].min_timestamp;
+                ov_lo.push_back(job->overlaps[i].token_lo);
+                ov_hi.push_back(job->overlaps[i].token_hi);
+                ov_ts.push_back(job->overlaps[i].min_timestamp);
                 any_bloom |= job->overlaps[i].bloom_bits != nullptr;
             }
-            d_ov_lo.alloc(job->n_overlaps * 8);
-            d_ov_hi.alloc(job->n_overlaps * 8);
-            d_ov_ts.alloc(job->n_overlaps * 8);
-            HIP_CHECK(hipMemcpyAsync(d_ov_lo.p, ov_lo_h.data(), job->n_overlaps * 8, hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(d_ov_hi.p, ov_hi_h.data(), job->n_overlaps * 8, hipMemcpyHostToDevice, stream));
-            HIP_CHECK(hipMemcpyAsync(d_ov_ts.p, ov_ts_h.data(), job->n_overlaps * 8, hipMemcpyHostToDevice, stream));
-            pp.ov_lo = d_ov_lo.as<int64_t>();
-            pp.ov_hi = d_ov_hi.as<int64_t>();
-            pp.ov_min_ts = d_ov_ts.as<int64_t>();
+            pp.ov_lo = upload(d_ov_lo, ov_lo.data(), ov_lo.size(), stream);
+            pp.ov_hi = upload(d_ov_hi, ov_hi.data(), ov_hi.size(), stream);
+            pp.ov_min_ts = upload(d_ov_ts, ov_ts.data(), ov_ts.size(), stream);
             if (any_bloom) {
-                // pack the per-overlap bloom bit arrays into one device
-                // buffer (word offsets per entry; bit_len 0 = no bloom)
+                // word offsets per entry; bit_len 0 = no bloom
                 for (int i = 0; i < job->n_overlaps; i++) {
                     const auto& ov = job->overlaps[i];
-                    ov_boff_h.push_back(ov_bw_h.size());
+                    ov_boff.push_back(ov_bw.size());
                     if (ov.bloom_bits && ov.bloom_bit_len) {
                         uint64_t words32 = (ov.bloom_bit_len + 31) / 32;
-                        ov_bw_h.insert(ov_bw_h.end(), ov.bloom_bits, ov.bloom_bits + words32);
-                        ov_bbits_h.push_back(ov.bloom_bit_len);
-                        ov_bk_h.push_back(ov.bloom_hash_count);
+                        ov_bw.insert(ov_bw.end(), ov.bloom_bits, ov.bloom_bits + words32);
+                        ov_bbits.push_back(ov.bloom_bit_len);
+                        ov_bk.push_back(ov.bloom_hash_count);
                     } else {
-                        ov_bbits_h.push_back(0);
-                        ov_bk_h.push_back(0);
+                        ov_bbits.push_back(0);
+                        ov_bk.push_back(0);
                     }
                 }
-                d_ov_bw.alloc(ov_bw_h.size() * 4 + 8);
-                d_ov_boff.alloc(ov_boff_h.size() * 8);
-                d_ov_bbits.alloc(ov_bbits_h.size() * 8);
-                d_ov_bk.alloc(ov_bk_h.size() * 4);
-                HIP_CHECK(hipMemcpyAsync(d_ov_bw.p, ov_bw_h.data(), ov_bw_h.size() * 4, hipMemcpyHostToDevice, stream));
-                HIP_CHECK(hipMemcpyAsync(d_ov_boff.p, ov_boff_h.data(), ov_boff_h.size() * 8, hipMemcpyHostToDevice, stream));
-                HIP_CHECK(hipMemcpyAsync(d_ov_bbits.p, ov_bbits_h.data(), ov_bbits_h.size() * 8, hipMemcpyHostToDevice, stream));
-                HIP_CHECK(hipMemcpyAsync(d_ov_bk.p, ov_bk_h.data(), ov_bk_h.size() * 4, hipMemcpyHostToDevice, stream));
-                pp.ov_bloom_words = d_ov_bw.as<uint32_t>();
-                pp.ov_bloom_off = d_ov_boff.as<uint64_t>();
-                pp.ov_bloom_bits = d_ov_bbits.as<uint64_t>();
-                pp.ov_bloom_k = d_ov_bk.as<int32_t>();
+                pp.ov_bloom_words = upload(d_ov_bw, ov_bw.data(), ov_bw.size(), stream, 8);
+                pp.ov_bloom_off = upload(d_ov_boff, ov_boff.data(), ov_boff.size(), stream);
+                pp.ov_bloom_bits = upload(d_ov_bbits, ov_bbits.data(), ov_bbits.size(), stream);
+                pp.ov_bloom_k = upload(d_ov_bk, ov_bk.data(), ov_bk.size(), stream);
                 pp.ov_has_bloom = 1;
             }
         }
-        HIP_CHECK(hipEventRecord(er0, stream));
-        // GC mode: purge is DEFERRED until after the garbage filter
-        // (GarbageSkipper runs before the Purger in CompactionIterator)
-        PurgeParams2 pp_data = pp;
-        if (gc_mode) {
-            pp_data.gc_before = INT64_MIN;
-            pp_data.never_purge = 1;
-            pp_data.enforce_strict_liveness = 0;
-        }
-        launch_reconcile(groups, kd, d_srcbases, parsed, rec, sch, pp_data, d_error, stream);
-        HIP_CHECK(hipEventRecord(er1, stream));
-        HIP_CHECK(hipEventRecord(e4, stream));
-        TR("reconcile issued");
-        if (unsigned long long err = read_dev_error(d_error, stream))
-            throw std::runtime_error("GPU reconcile error code " + std::to_string(err));
-
-        // ---- garbage collect: merge the tombstone sources, filter, purge ----
-        UnfColsBuf gc_rows;          // filtered data arena (replaces out_rows)
-        UnfColsBuf* rows_for_writer = &out_rows;
-        Groups groups_t;     // tombstone sources, reconciled among themselves
-        Reconciled rec_t;
-        DevBuf d_ctr_arena_t;
-        if (gc_mode && n_groups > 0) {
-            uint64_t src_parts = total_parts - data_parts;
-            if (src_parts > 0) {
-                std::vector<uint64_t> runs_t;
-                runs_t.push_back(0);
-                for (int s2 = kd; s2 < k; s2++) runs_t.push_back(runs_t.back() + srcs[s2].n_parts);
-                MRec* d_sorted_t = merge_sorted_runs(d_recs_a.as<MRec>() + data_parts,
-                                                     d_recs_b.as<MRec>() + data_parts, runs_t,
-                                                     stream, lut);
-                find_groups(groups_t, d_sorted_t, src_parts, lut, stream);
-                scan_group_rows(groups_t, d_srcbases, pc, stream);
-                rec_t.alloc(groups_t, sch, total_in_cpx, stream);
-                // the source pass bump-allocates merged counter contexts from
-                // its own arena (the main pass's bump counter lives in the
-                // OTHER OutStats, so sharing one arena would overlap)
-                SchemaParams sch_t = sch;
-                if (sch.counters) {
-                    d_ctr_arena_t.alloc(ctr_arena_cap);
-                    sch_t.ctr_arena = d_ctr_arena_t.as<uint8_t>();
-                }
-                PurgeParams2 pp_src = pp_data;
-                pp_src.has_shard = 0;  // sources shadow regardless of the shard
-                pp_src.group_leaf = nullptr;  // indexed by the data groups, not these
-                launch_reconcile(groups_t, k - kd, d_srcbases, parsed, rec_t, sch_t, pp_src,
-                                 d_error, stream);
-            }
-            const OutPartsBuf& opb_t = rec_t.parts;
-            const UnfColsBuf& out_rows_t = rec_t.rows;
-            const uint64_t n_groups_t = groups_t.n;
-            // match + capacity scan + filter
-            DevBuf d_tidx, d_cap;
-            d_tidx.alloc(n_groups * 8);
-            d_cap.alloc(n_groups * 8);
-            {
-                uint32_t blocks_g = (uint32_t)((n_groups + 255) / 256);
-                hipLaunchKernelGGL(k_gc_match, dim3(blocks_g), dim3(256), 0, stream, opb.op,
-                                   n_groups, opb_t.op, n_groups_t, d_tidx.as<int64_t>(),
-                                   d_cap.as<uint64_t>());
-            }
-            uint64_t gc_total = exscan_u64(d_cap.as<uint64_t>(), n_groups, stream);
-            gc_rows.alloc(gc_total, sch.n_cols, sch.n_ck, sch.n_cpx);
-            // the cpx CELL arena is shared: the filter compacts each row's
-            // own [start,count) segment of out_rows' arena in place
-            if (sch.n_cpx) gc_rows.uc.cpx = out_rows.uc.cpx;
-            {
-                uint32_t blocks_g = (uint32_t)((n_groups + 255) / 256);
-                hipLaunchKernelGGL(k_garbage_filter, dim3(blocks_g), dim3(256), 0, stream, opb.op,
-                                   n_groups, opb_t.op, out_rows.uc, out_rows_t.uc, gc_rows.uc,
-                                   d_tidx.as<int64_t>(), d_cap.as<uint64_t>(), sch, parsed.cx,
-                                   job->cell_level_gc ? 1 : 0);
-            }
-            // reset first/last group, then the deferred purge pass
-            HIP_CHECK(hipMemsetAsync((uint8_t*)d_stats.p + offsetof(OutStats, first_group), 0xFF, 8, stream));
-            HIP_CHECK(hipMemsetAsync((uint8_t*)d_stats.p + offsetof(OutStats, last_group), 0x00, 8, stream));
-            {
-                uint32_t blocks_g = (uint32_t)((n_groups + 255) / 256);
-                hipLaunchKernelGGL(k_purge_parts, dim3(blocks_g), dim3(256), 0, stream, opb.op,
-                                   gc_rows.uc, n_groups, sch, pp, d_stats.as<OutStats>());
-            }
-            if (unsigned long long err = read_dev_error(d_error, stream))
-                throw std::runtime_error("GPU gc filter error code " + std::to_string(err));
-            rows_for_writer = &gc_rows;
-            TR("garbage filtered");
-        }
-
-        // ---- output header (SerializationHeader.make: desc-generation stats merge) ----
-        SerParams2 sp2{};
-        sp2.sch = sch;
-        {
-            std::vector<int> order(kd);
-            for (int s = 0; s < kd; s++) order[s] = s;
-            std::stable_sort(order.begin(), order.end(),
-                             [&](int a, int b) { return generations[a] > generations[b]; });
-            int64_t min_ts = INT64_MAX, min_ldt = INT64_MAX;
-            int32_t min_ttl = INT32_MAX;
-            for (int s : order) {
-                min_ts = std::min(min_ts, stats[s].min_timestamp);
-                min_ldt = std::min(min_ldt, stats[s].min_ldt);
-                min_ttl = std::min(min_ttl, stats[s].min_ttl);
-            }
-            sp2.hs.min_ts = min_ts == NO_TIMESTAMP ? TIMESTAMP_EPOCH : min_ts;
-            sp2.hs.min_ldt = min_ldt == NO_DELETION_TIME ? DELETION_TIME_EPOCH : min_ldt;
-            sp2.hs.min_ttl = min_ttl == INT32_MAX ? 0 : min_ttl;
-        }
-        restore_ck_ascending(opb.op, *rows_for_writer, n_groups, sch, stream);
-        if (g_validate_out) {
-            // VALIDATION epilogue: per-partition repair digests instead of a
-            // written sstable (k_validate_digest; Validator.rowHash)
-            ValidateNames vnames;
-            ValidateParams vpar = vnames.upload(su.js.header, sch, stream);
-            DevBuf d_hash;
-            d_hash.alloc(n_groups * 32 + 32);
-            {
-                uint32_t blocks2 = (uint32_t)((n_groups + 255) / 256);
-                hipLaunchKernelGGL(k_validate_digest, dim3(blocks2), dim3(256), 0, stream, opb.op,
-                                   rows_for_writer->uc, n_groups, vpar, d_hash.as<uint8_t>());
-            }
-            std::vector<uint8_t> h_hash(n_groups * 32);
-            std::vector<int64_t> h_tok(n_groups);
-            std::vector<uint8_t> h_keep(n_groups);
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(h_hash.data(), d_hash.p, n_groups * 32, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(h_tok.data(), opb.op.token, n_groups * 8, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(h_keep.data(), opb.op.keep, n_groups, hipMemcpyDeviceToHost));
-            bytes outb;
-            uint64_t cnt = 0;
-            for (uint64_t g2 = 0; g2 < n_groups; g2++) {
-                if (!h_keep[g2]) continue;
-                for (int b2 = 7; b2 >= 0; b2--) outb.push_back((uint8_t)((uint64_t)h_tok[g2] >> (8 * b2)));
-                outb.insert(outb.end(), h_hash.begin() + g2 * 32, h_hash.begin() + g2 * 32 + 32);
-                cnt++;
-            }
-            write_file(g_validate_out, outb.data(), outb.size());
-            g_validate_count = cnt;
-            {
-                std::lock_guard<std::mutex> gl(res_mu);
-                res->partitions_out += cnt;
-            }
-            return;
-        }
-        if (g_merkle) {
-            // MERKLE epilogue: the same digests, XORed into their leaves on
-            // the device; only the leaves travel to the host
-            ValidateNames vnames;
-            ValidateParams vpar = vnames.upload(su.js.header, sch, stream);
-            DevBuf d_hash, d_leaves;
-            d_hash.alloc(n_groups * 32 + 32);
-            // n_leaves x 4 hash words, then n_leaves counts
-            d_leaves.alloc((uint64_t)mk_leaves * 40);
-            HIP_CHECK(hipMemsetAsync(d_leaves.p, 0, (uint64_t)mk_leaves * 40, stream));
-            unsigned long long* d_lh = d_leaves.as<unsigned long long>();
-            unsigned long long* d_lc = d_lh + (uint64_t)mk_leaves * 4;
-            if (n_groups) {
-                uint32_t blocks2 = (uint32_t)((n_groups + 255) / 256);
-                hipLaunchKernelGGL(k_validate_digest, dim3(blocks2), dim3(256), 0, stream, opb.op,
-                                   rows_for_writer->uc, n_groups, vpar, d_hash.as<uint8_t>());
-                hipLaunchKernelGGL(k_merkle_leaf_xor, dim3(blocks2), dim3(256), 0, stream,
-                                   opb.op.keep, d_group_leaf.as<int32_t>(),
-                                   d_hash.as<uint64_t>(), n_groups, d_lh, d_lc);
-            }
-            std::vector<uint64_t> h_cnt(mk_leaves);
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(g_merkle->leaf_hash, d_lh, (uint64_t)mk_leaves * 32, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(h_cnt.data(), d_lc, (uint64_t)mk_leaves * 8, hipMemcpyDeviceToHost));
-            uint64_t cnt = 0;
-            for (uint32_t i = 0; i < mk_leaves; i++) cnt += h_cnt[i];
-            if (g_merkle->leaf_partitions)
-                memcpy(g_merkle->leaf_partitions, h_cnt.data(), (uint64_t)mk_leaves * 8);
-            g_merkle->n_partitions = cnt;
-            {
-                std::lock_guard<std::mutex> gl(res_mu);
-                res->partitions_out += cnt;
-            }
-            return;
-        }
-        const OutputOptions oopt{out_base_str, su.cinfos[0].snappy, su.bti, su.out_chunk_len, wslot};
-        WriteDeviceOut w;
-        if (g_route) {
-            // ROUTED outputs: classify the kept partitions by token once, then
-            // run the writer once per output under that output's keep mask
-            const gpuc_route_spec& rs = *g_route->spec;
-            const uint32_t n_out = rs.n_outputs;
-            DevBuf d_rlo, d_rhi, d_rout, d_cls, d_mask, d_cnt, d_stats_o;
-            d_rlo.alloc((uint64_t)rs.n_ranges * 8 + 8);
-            d_rhi.alloc((uint64_t)rs.n_ranges * 8 + 8);
-            d_rout.alloc((uint64_t)rs.n_ranges * 4 + 4);
-            d_cls.alloc(n_groups + 1);
-            d_mask.alloc(n_groups + 1);
-            d_cnt.alloc((uint64_t)n_out * 8);
-            d_stats_o.alloc(sizeof(OutStats));
-            if (rs.n_ranges) {
-                HIP_CHECK(hipMemcpyAsync(d_rlo.p, rs.range_lo, (uint64_t)rs.n_ranges * 8, hipMemcpyHostToDevice, stream));
-                HIP_CHECK(hipMemcpyAsync(d_rhi.p, rs.range_hi, (uint64_t)rs.n_ranges * 8, hipMemcpyHostToDevice, stream));
-                HIP_CHECK(hipMemcpyAsync(d_rout.p, rs.range_output, (uint64_t)rs.n_ranges * 4, hipMemcpyHostToDevice, stream));
-            }
-            HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (uint64_t)n_out * 8, stream));
-            const uint32_t blocks_r = (uint32_t)((n_groups + 255) / 256);
-            if (n_groups) {
-                RouteParams rp{d_rlo.as<int64_t>(), d_rhi.as<int64_t>(), d_rout.as<int32_t>(),
-                               rs.n_ranges, rs.default_output, n_out};
-                hipLaunchKernelGGL(k_route_parts, dim3(blocks_r), dim3(256), 0, stream,
-                                   opb.op.token, opb.op.keep, n_groups, rp, d_cls.as<uint8_t>(),
-                                   d_cnt.as<unsigned long long>());
-            }
-            std::vector<uint64_t> h_cnt(n_out);
-            HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipMemcpy(h_cnt.data(), d_cnt.p, (uint64_t)n_out * 8, hipMemcpyDeviceToHost));
-            w.n_outputs = 0;
-            OutParts view = opb.op;
-            view.keep = d_mask.as<uint8_t>();
-            for (uint32_t o = 0; o < n_out; o++) {
-                gpuc_route_output ro{};
-                if (h_cnt[o]) {
-                    check_cancel(job);
-                    hipLaunchKernelGGL(k_route_mask, dim3(blocks_r), dim3(256), 0, stream,
-                                       d_cls.as<uint8_t>(), n_groups, (uint8_t)o,
-                                       d_mask.as<uint8_t>());
-                    init_outstats(d_stats_o, stream);
-                    OutputOptions oopt_o = oopt;
-                    oopt_o.base = rs.output_bases[o];
-                    WriteDeviceOut wo =
-                        write_sstable_device(view, *rows_for_writer, n_groups, sp2, d_stats_o,
-                                             d_tomb, tomb_cap, su.js.header, oopt_o, stream);
-                    if (wo.partitions != h_cnt[o])
-                        throw std::runtime_error("routed output " + std::to_string(o) +
-                                                 ": writer and router disagree on partitions");
-                    ro.written = 1;
-                    ro.partitions = wo.partitions;
-                    ro.rows = wo.rows;
-                    ro.uncompressed_bytes = wo.uncompressed_len;
-                    ro.compressed_bytes = wo.compressed_len;
-                    w.n_outputs++;
-                    w.partitions += wo.partitions;
-                    w.rows += wo.rows;
-                    w.cells += wo.cells;
-                    w.uncompressed_len += wo.uncompressed_len;
-                    w.compressed_len += wo.compressed_len;
-                    w.ms_sizes += wo.ms_sizes;
-                    w.ms_serialize += wo.ms_serialize;
-                    w.ms_compress += wo.ms_compress;
-                    w.ms_d2h += wo.ms_d2h;
-                    w.ms_io += wo.ms_io;
-                }
-                if (g_route->outputs) g_route->outputs[o] = ro;
-            }
-        } else if (job->max_output_bytes) {
-            // r of the speculative window: the inputs' own compressed/uncompressed ratio
-            uint64_t in_comp = 0, in_unc = 0;
-            for (int s = 0; s < kd; s++) {
-                in_comp += su.comp_file_sz[s];
-                in_unc += cinfos[s].data_len;
-            }
-            w = write_sstables_size_split(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
-                                          tomb_cap, su.js.header, oopt, job->max_output_bytes,
-                                          in_unc ? (double)in_comp / (double)in_unc : 1.0,
-                                          [&]() { check_cancel(job); }, stream);
-        } else {
-            w = write_sstable_device(opb, *rows_for_writer, n_groups, sp2, d_stats, d_tomb,
-                                     tomb_cap, su.js.header, oopt, stream);
-        }
-        TR("writer done");
-        {
-            OutStats hst;
-            HIP_CHECK(hipMemcpy(&hst, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
-            float th2d, tdec, tparse, tmerge, trec;
-            HIP_CHECK(hipEventElapsedTime(&th2d, e0, e1));
-            HIP_CHECK(hipEventElapsedTime(&tdec, e1, e2));
-            HIP_CHECK(hipEventElapsedTime(&tparse, e2, e3));
-            HIP_CHECK(hipEventElapsedTime(&tmerge, e3, e4));
-            HIP_CHECK(hipEventElapsedTime(&trec, er0, er1));
-            std::lock_guard<std::mutex> g(res_mu);
-            res->n_outputs += w.n_outputs;
-            res->partitions_out += w.partitions;
-            res->rows_out += w.rows;
-            res->output_uncompressed_bytes += w.uncompressed_len;
-            res->output_compressed_bytes += w.compressed_len;
-            for (int i = 0; i < 64; i++) res->merged_counts[i] += hst.merged_counts[i];
-            res->ms_h2d = 0;         // overlapped into the ingest pipeline (e0..e1)
-            res->ms_decompress += th2d + tdec;  // read/H2D/decompress pipeline, GPU side
-            res->ms_parse += tparse;
-            res->ms_reconcile += trec;
-            res->ms_merge += tmerge - trec;  // merge rounds + grouping
-            res->ms_serialize += w.ms_sizes + w.ms_serialize;
-            res->ms_compress += w.ms_compress;
-            res->ms_d2h += w.ms_d2h;
-            res->ms_write_io += w.ms_io;
-            // dominant kernel estimate
-            struct { const char* n; double ms; } ks[] = {
-                {"k_lz4_decompress", (double)th2d + tdec}, {"k_parse", (double)tparse},
-                {"merge+reconcile", (double)tmerge},
-                {"k_serialize", w.ms_serialize}, {"k_lz4_compress", w.ms_compress}};
-            for (auto& kk : ks)
-                if (kk.ms > res->dominant_kernel_ms) {
-                    res->dominant_kernel_ms = kk.ms;
-                    snprintf(res->dominant_kernel, sizeof(res->dominant_kernel), "%s", kk.n);
-                }
-            res->dominant_kernel_launches = 1;
-        }
+        return pp;
     }
+};
+
+// Merkle device side. assign() gives every group its leaf BEFORE reconcile,
+// which then drops the partitions of no tree instead of merging them;
+// reduce() XORs the digests into their leaves after it, so that only the
+// leaves travel to the host. The spec's arrays are the caller's.
+struct MerkleLeaves {
+    DevBuf d_left, d_begin, d_right, d_group_leaf;
+    uint32_t n_leaves = 0;
+    const int32_t* assign(const gpuc_merkle_spec& ms, const Groups& groups, hipStream_t stream) {
+        n_leaves = ms.leaf_begin[ms.n_trees];
+        MerkleParams mp{upload(d_left, ms.tree_left, (size_t)ms.n_trees, stream),
+                        upload(d_begin, ms.leaf_begin, (size_t)ms.n_trees + 1, stream),
+                        upload(d_right, ms.leaf_right, (size_t)n_leaves, stream), ms.n_trees};
+        d_group_leaf.alloc(groups.n * 4 + 4);
+        if (groups.n)
+            hipLaunchKernelGGL(k_merkle_assign, dim3((uint32_t)((groups.n + 255) / 256)),
+                               dim3(256), 0, stream, groups.sorted,
+                               groups.start.as<uint64_t>(), groups.n, mp,
+                               d_group_leaf.as<int32_t>());
+        return d_group_leaf.as<int32_t>();
+    }
+    // the MERKLE epilogue; synchronises. Returns the partitions digested.
+    uint64_t reduce(MerkleRun& run, const TableTypes& header, const SchemaParams& sch,
+                    const OutParts& op, const UnfColsBuf& rows, uint64_t n_groups,
+                    hipStream_t stream) {
+        ValidateNames vnames;
+        ValidateParams vpar = vnames.upload(header, sch, stream);
+        DevBuf d_hash, d_leaves;
+        // n_leaves x 4 hash words, then n_leaves counts
+        d_leaves.alloc((uint64_t)n_leaves * 40);
+        HIP_CHECK(hipMemsetAsync(d_leaves.p, 0, (uint64_t)n_leaves * 40, stream));
+        unsigned long long* d_lh = d_leaves.as<unsigned long long>();
+        unsigned long long* d_lc = d_lh + (uint64_t)n_leaves * 4;
+        launch_validate_digest(op, rows, n_groups, vpar, d_hash, stream);
+        if (n_groups)
+            hipLaunchKernelGGL(k_merkle_leaf_xor, dim3((uint32_t)((n_groups + 255) / 256)),
+                               dim3(256), 0, stream, op.keep, d_group_leaf.as<int32_t>(),
+                               d_hash.as<uint64_t>(), n_groups, d_lh, d_lc);
+        std::vector<uint64_t> h_cnt(n_leaves);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        HIP_CHECK(hipMemcpy(run.leaf_hash, d_lh, (uint64_t)n_leaves * 32, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(h_cnt.data(), d_lc, (uint64_t)n_leaves * 8, hipMemcpyDeviceToHost));
+        uint64_t cnt = 0;
+        for (uint32_t i = 0; i < n_leaves; i++) cnt += h_cnt[i];
+        if (run.leaf_partitions) memcpy(run.leaf_partitions, h_cnt.data(), (uint64_t)n_leaves * 8);
+        run.n_partitions = cnt;
+        return cnt;
+    }
+};
+
+// The VALIDATION epilogue: per-partition repair digests of the kept groups
+// (8-byte BE token + 32-byte hash each) written to `path` instead of an
+// sstable. Synchronises. Returns the partitions digested.
+static uint64_t write_digest_file(const char* path, const TableTypes& header,
+                                  const SchemaParams& sch, const OutParts& op,
+                                  const UnfColsBuf& rows, uint64_t n_groups, hipStream_t stream) {
+    ValidateNames vnames;
+    ValidateParams vpar = vnames.upload(header, sch, stream);
+    DevBuf d_hash;
+    launch_validate_digest(op, rows, n_groups, vpar, d_hash, stream);
+    std::vector<uint8_t> h_hash(n_groups * 32);
+    std::vector<int64_t> h_tok(n_groups);
+    std::vector<uint8_t> h_keep(n_groups);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(h_hash.data(), d_hash.p, n_groups * 32, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_tok.data(), op.token, n_groups * 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h_keep.data(), op.keep, n_groups, hipMemcpyDeviceToHost));
+    bytes outb;
+    uint64_t cnt = 0;
+    for (uint64_t g2 = 0; g2 < n_groups; g2++) {
+        if (!h_keep[g2]) continue;
+        for (int b2 = 7; b2 >= 0; b2--) outb.push_back((uint8_t)((uint64_t)h_tok[g2] >> (8 * b2)));
+        outb.insert(outb.end(), h_hash.begin() + g2 * 32, h_hash.begin() + g2 * 32 + 32);
+        cnt++;
+    }
+    write_file(path, outb.data(), outb.size());
+    return cnt;
 }
 
+// Garbage-collect pass (kd < k): the tombstone sources are merged and
+// reconciled among themselves, matched against the data groups, the shadowed
+// data is filtered out into `rows`, and the purge that the data pass deferred
+// runs last (GarbageSkipper runs before the Purger in CompactionIterator).
+// Synchronises to read d_error. `rows` replaces the data pass's rows for the
+// writer and shares their complex-cell arena.
+struct GarbageCollect {
+    UnfColsBuf rows;
+    Groups groups_t;  // tombstone sources, reconciled among themselves
+    Reconciled rec_t;
+    DevBuf d_ctr_arena_t;
+    void run(const gpuc_job* job, const std::vector<uint64_t>& runs_t, MRec* d_recs_a,
+             MRec* d_recs_b, const KeyLut& lut, const DevBuf& d_srcbases,
+             const ParsedInput& parsed, const SchemaParams& sch, uint64_t ctr_arena_cap,
+             const PurgeParams2& pp, const PurgeParams2& pp_data, Reconciled& rec,
+             uint64_t n_groups, const DevBuf& d_error, hipStream_t stream) {
+        const OutParts& op = rec.parts.op;
+        const uint64_t src_parts = runs_t.back();
+        if (src_parts > 0) {
+            MRec* d_sorted_t = merge_sorted_runs(d_recs_a, d_recs_b, runs_t, stream, lut);
+            find_groups(groups_t, d_sorted_t, src_parts, lut, stream);
+            scan_group_rows(groups_t, d_srcbases, parsed.pc, stream);
+            rec_t.alloc(groups_t, sch, parsed.total_cpx, stream);
+            // the source pass bump-allocates merged counter contexts from
+            // its own arena (the main pass's bump counter lives in the
+            // OTHER OutStats, so sharing one arena would overlap)
+            SchemaParams sch_t = sch;
+            if (sch.counters) {
+                d_ctr_arena_t.alloc(ctr_arena_cap);
+                sch_t.ctr_arena = d_ctr_arena_t.as<uint8_t>();
+            }
+            PurgeParams2 pp_src = pp_data;
+            pp_src.has_shard = 0;  // sources shadow regardless of the shard
+            pp_src.group_leaf = nullptr;  // indexed by the data groups, not these
+            launch_reconcile(groups_t, (int)runs_t.size() - 1, d_srcbases, parsed, rec_t, sch_t,
+                             pp_src, d_error, stream);
+        }
+        // match + capacity scan + filter
+        const dim3 grid((uint32_t)((n_groups + 255) / 256)), block(256);
+        DevBuf d_tidx, d_cap;
+        d_tidx.alloc(n_groups * 8);
+        d_cap.alloc(n_groups * 8);
+        hipLaunchKernelGGL(k_gc_match, grid, block, 0, stream, op, n_groups, rec_t.parts.op,
+                           groups_t.n, d_tidx.as<int64_t>(), d_cap.as<uint64_t>());
+        uint64_t gc_total = exscan_u64(d_cap.as<uint64_t>(), n_groups, stream);
+        rows.alloc(gc_total, sch.n_cols, sch.n_ck, sch.n_cpx);
+        // the cpx CELL arena is shared: the filter compacts each row's
+        // own [start,count) segment of the data rows' arena in place
+        if (sch.n_cpx) rows.uc.cpx = rec.rows.uc.cpx;
+        hipLaunchKernelGGL(k_garbage_filter, grid, block, 0, stream, op, n_groups, rec_t.parts.op,
+                           rec.rows.uc, rec_t.rows.uc, rows.uc, d_tidx.as<int64_t>(),
+                           d_cap.as<uint64_t>(), sch, parsed.cx, job->cell_level_gc ? 1 : 0);
+        // reset first/last group, then the deferred purge pass
+        HIP_CHECK(hipMemsetAsync((uint8_t*)rec.stats.p + offsetof(OutStats, first_group), 0xFF, 8, stream));
+        HIP_CHECK(hipMemsetAsync((uint8_t*)rec.stats.p + offsetof(OutStats, last_group), 0x00, 8, stream));
+        hipLaunchKernelGGL(k_purge_parts, grid, block, 0, stream, op, rows.uc, n_groups, sch, pp,
+                           rec.stats.as<OutStats>());
+        if (unsigned long long err = read_dev_error(d_error, stream))
+            throw std::runtime_error("GPU gc filter error code " + std::to_string(err));
+    }
+};
+
+// the output header's minima (SerializationHeader.make merges the compacted
+// inputs' EncodingStats; a minimum does not depend on their order)
+static HeaderStats merged_header_stats(const std::vector<HStatistics>& stats, int kd) {
+    int64_t min_ts = INT64_MAX, min_ldt = INT64_MAX;
+    int32_t min_ttl = INT32_MAX;
+    for (int s = 0; s < kd; s++) {
+        min_ts = std::min(min_ts, stats[s].min_timestamp);
+        min_ldt = std::min(min_ldt, stats[s].min_ldt);
+        min_ttl = std::min(min_ttl, stats[s].min_ttl);
+    }
+    HeaderStats hs;
+    hs.min_ts = min_ts == NO_TIMESTAMP ? TIMESTAMP_EPOCH : min_ts;
+    hs.min_ldt = min_ldt == NO_DELETION_TIME ? DELETION_TIME_EPOCH : min_ldt;
+    hs.min_ttl = min_ttl == INT32_MAX ? 0 : min_ttl;
+    return hs;
+}
+
+// What the writing epilogues consume: the reconciled partitions, the rows
+// that survived (the garbage-collect pass's, when it ran), the header, and
+// the stats and tombstone list that reconcile filled.
+struct MergedOutput {
+    const OutPartsBuf& parts;
+    const UnfColsBuf& rows;
+    uint64_t n_groups;
+    SerParams2 sp;
+    DevBuf& stats;
+    DevBuf& tomb;
+    uint32_t tomb_cap;
+};
+
+// ROUTED outputs: classify the kept partitions by token once, then run the
+// writer once per output under that output's keep mask. Synchronises to read
+// the per-output counts; polls for cancellation between outputs.
+static WriteDeviceOut write_routed_outputs(const gpuc_job* job, RouteRun& run,
+                                           const MergedOutput& m, const TableTypes& header,
+                                           const OutputOptions& oopt, hipStream_t stream) {
+    const gpuc_route_spec& rs = *run.spec;
+    const uint32_t n_out = rs.n_outputs;
+    const uint64_t n_groups = m.n_groups;
+    DevBuf d_rlo, d_rhi, d_rout, d_cls, d_mask, d_cnt, d_stats_o;
+    RouteParams rp{upload(d_rlo, rs.range_lo, (size_t)rs.n_ranges, stream, 8),
+                   upload(d_rhi, rs.range_hi, (size_t)rs.n_ranges, stream, 8),
+                   upload(d_rout, rs.range_output, (size_t)rs.n_ranges, stream, 4),
+                   rs.n_ranges, rs.default_output, n_out};
+    d_cls.alloc(n_groups + 1);
+    d_mask.alloc(n_groups + 1);
+    d_cnt.alloc((uint64_t)n_out * 8);
+    d_stats_o.alloc(sizeof(OutStats));
+    HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, (uint64_t)n_out * 8, stream));
+    const dim3 grid((uint32_t)((n_groups + 255) / 256)), block(256);
+    if (n_groups)
+        hipLaunchKernelGGL(k_route_parts, grid, block, 0, stream, m.parts.op.token,
+                           m.parts.op.keep, n_groups, rp, d_cls.as<uint8_t>(),
+                           d_cnt.as<unsigned long long>());
+    std::vector<uint64_t> h_cnt(n_out);
+    HIP_CHECK(hipStreamSynchronize(stream));
+    HIP_CHECK(hipMemcpy(h_cnt.data(), d_cnt.p, (uint64_t)n_out * 8, hipMemcpyDeviceToHost));
+    WriteDeviceOut w;
+    w.n_outputs = 0;
+    OutParts view = m.parts.op;
+    view.keep = d_mask.as<uint8_t>();
+    for (uint32_t o = 0; o < n_out; o++) {
+        gpuc_route_output ro{};
+        if (h_cnt[o]) {
+            check_cancel(job);
+            hipLaunchKernelGGL(k_route_mask, grid, block, 0, stream, d_cls.as<uint8_t>(), n_groups,
+                               (uint8_t)o, d_mask.as<uint8_t>());
+            init_outstats(d_stats_o, stream);
+            OutputOptions oopt_o = oopt;
+            oopt_o.base = rs.output_bases[o];
+            WriteDeviceOut wo = write_sstable_device(view, m.rows, n_groups, m.sp, d_stats_o,
+                                                     m.tomb, m.tomb_cap, header, oopt_o, stream);
+            if (wo.partitions != h_cnt[o])
+                throw std::runtime_error("routed output " + std::to_string(o) +
+                                         ": writer and router disagree on partitions");
+            ro.written = 1;
+            ro.partitions = wo.partitions;
+            ro.rows = wo.rows;
+            ro.uncompressed_bytes = wo.uncompressed_len;
+            ro.compressed_bytes = wo.compressed_len;
+            w.add(wo);
+        }
+        if (run.outputs) run.outputs[o] = ro;
+    }
+    return w;
+}
+
+// one sstable, or several cut at job->max_output_bytes
+static WriteDeviceOut write_plain_or_split(const gpuc_job* job, const CompactSetup& su, int kd,
+                                           const MergedOutput& m, const OutputOptions& oopt,
+                                           hipStream_t stream) {
+    if (!job->max_output_bytes)
+        return write_sstable_device(m.parts, m.rows, m.n_groups, m.sp, m.stats, m.tomb,
+                                    m.tomb_cap, su.js.header, oopt, stream);
+    // r of the speculative window: the inputs' own compressed/uncompressed ratio
+    uint64_t in_comp = 0, in_unc = 0;
+    for (int s = 0; s < kd; s++) {
+        in_comp += su.comp_file_sz[s];
+        in_unc += su.cinfos[s].data_len;
+    }
+    return write_sstables_size_split(m.parts, m.rows, m.n_groups, m.sp, m.stats, m.tomb,
+                                     m.tomb_cap, su.js.header, oopt, job->max_output_bytes,
+                                     in_unc ? (double)in_comp / (double)in_unc : 1.0,
+                                     [&]() { check_cancel(job); }, stream);
+}
+
+// Result accounting of a writing run: phase times from the events (all long
+// complete: the writer has drained), the writer's totals, and merged_counts
+// from RECONCILE's stats (a routed run's per-output stats never hold them).
+static void account_result(gpuc_result* res, std::mutex& res_mu, const PhaseEvents& ev,
+                           const WriteDeviceOut& w, const DevBuf& d_stats) {
+    OutStats hst;
+    HIP_CHECK(hipMemcpy(&hst, d_stats.p, sizeof(OutStats), hipMemcpyDeviceToHost));
+    float th2d, tdec, tparse, tmerge, trec;
+    HIP_CHECK(hipEventElapsedTime(&th2d, ev.e0, ev.e1));
+    HIP_CHECK(hipEventElapsedTime(&tdec, ev.e1, ev.e2));
+    HIP_CHECK(hipEventElapsedTime(&tparse, ev.e2, ev.e3));
+    HIP_CHECK(hipEventElapsedTime(&tmerge, ev.e3, ev.e4));
+    HIP_CHECK(hipEventElapsedTime(&trec, ev.er0, ev.er1));
+    std::lock_guard<std::mutex> g(res_mu);
+    res->n_outputs += w.n_outputs;
+    res->partitions_out += w.partitions;
+    res->rows_out += w.rows;
+    res->output_uncompressed_bytes += w.uncompressed_len;
+    res->output_compressed_bytes += w.compressed_len;
+    for (int i = 0; i < 64; i++) res->merged_counts[i] += hst.merged_counts[i];
+    res->ms_h2d = 0;         // overlapped into the ingest pipeline (e0..e1)
+    res->ms_decompress += th2d + tdec;  // read/H2D/decompress pipeline, GPU side
+    res->ms_parse += tparse;
+    res->ms_reconcile += trec;
+    res->ms_merge += tmerge - trec;  // merge rounds + grouping
+    res->ms_serialize += w.ms_sizes + w.ms_serialize;
+    res->ms_compress += w.ms_compress;
+    res->ms_d2h += w.ms_d2h;
+    res->ms_write_io += w.ms_io;
+    // dominant kernel estimate
+    struct { const char* n; double ms; } ks[] = {
+        {"k_lz4_decompress", (double)th2d + tdec}, {"k_parse", (double)tparse},
+        {"merge+reconcile", (double)tmerge},
+        {"k_serialize", w.ms_serialize}, {"k_lz4_compress", w.ms_compress}};
+    for (auto& kk : ks)
+        if (kk.ms > res->dominant_kernel_ms) {
+            res->dominant_kernel_ms = kk.ms;
+            snprintf(res->dominant_kernel, sizeof(res->dominant_kernel), "%s", kk.n);
+        }
+    res->dominant_kernel_launches = 1;
+}
+
+// Everything from data read through component write for ONE shard window:
+// the pipeline, top to bottom. `mode` says what comes out at the end.
+static void compact_one(const gpuc_job* job, const CompactSetup& su, const ShardWindow& sw,
+                        const CompactMode& mode, gpuc_result* res, std::mutex& res_mu) {
+    HIP_CHECK(hipSetDevice(job->device));
+    Stream stream;  // ahead of every buffer used on it
+    const int k = su.k;
+
+    // ---- window ingest: read, H2D + decompress (pipelined per sstable) ----
+    double t0 = wall_ms();
+    WindowIngest ingest;
+    ingest.resolve(su, sw);
+    {
+        std::lock_guard<std::mutex> g(res_mu);
+        res->ms_read_io += wall_ms() - t0;
+    }
+    TR("window resolved");
+    check_cancel(job);
+    PhaseEvents ev;
+    HIP_CHECK(hipEventRecord(ev.e0, stream));
+    DevBuf d_error;
+    d_error.alloc(8);
+    HIP_CHECK(hipMemsetAsync(d_error.p, 0, 8, stream));
+    {
+        double ms_read_data = ingest.issue(su, d_error, stream);
+        std::lock_guard<std::mutex> g(res_mu);
+        res->ms_read_io += ms_read_data;  // residual read wait not hidden by the pipeline
+    }
+    TR("ingest issued");
+    HIP_CHECK(hipEventRecord(ev.e1, stream));  // e0..e1: H2D+decompress pipeline (overlapped)
+    HIP_CHECK(hipEventRecord(ev.e2, stream));
+    // corrupt inputs must fail cleanly, not fault the GPU: the parse
+    // walk trusts decompressed bytes, so the chunk-CRC verdict is checked
+    // BEFORE any parse kernel touches them
+    if (unsigned long long err = read_dev_error(d_error, stream))
+        throw std::runtime_error("input chunk decompress/CRC failed, code " + std::to_string(err));
+
+    // ---- parse (pass A: count + partition meta; pass B: row decode) ----
+    std::vector<SrcDesc2> srcs;  // read by an async copy: lives past the parse sync
+    const uint64_t total_parts = ingest.source_descs(su, srcs);
+    DevSchema dsch;
+    SchemaParams sch = dsch.upload(su.js.schema, stream);
+    DevBuf d_srcs, d_recs_a, d_recs_b, d_rows_in;
+    upload(d_srcs, srcs.data(), srcs.size(), stream);
+    d_recs_a.alloc(total_parts * sizeof(MRec));
+    d_recs_b.alloc(total_parts * sizeof(MRec));
+    d_rows_in.alloc(8);
+    HIP_CHECK(hipMemsetAsync(d_rows_in.p, 0, 8, stream));
+    ParsedInput parsed;
+    parsed.cx = cpx_types(su.js.schema);
+    parse_input(parsed, d_srcs, (uint32_t)k, total_parts, d_recs_a, sch, d_error, d_rows_in, false,
+                stream);
+    HIP_CHECK(hipEventRecord(ev.e3, stream));
+    {
+        unsigned long long err = read_dev_error(d_error, stream);
+        TR("parse synced");
+        check_cancel(job);  // a set cancel flag takes precedence over a parse error
+        throw_if_collection_parse_error(err);
+        if (err) throw std::runtime_error("GPU decode/parse error code " + std::to_string(err));
+        uint64_t rows_in_local = 0;
+        HIP_CHECK(hipMemcpy(&rows_in_local, d_rows_in.p, 8, hipMemcpyDeviceToHost));
+        std::lock_guard<std::mutex> g(res_mu);
+        res->rows_in += rows_in_local;
+    }
+
+    // ---- merge (pairwise rounds over pre-sorted source runs) ----
+    // In garbage-collect mode the first k_data inputs are the compacted
+    // data; the rest are tombstone sources merged in a second pass.
+    const KeyLut lut = ingest.key_lut();
+    const int kd = su.k_data > 0 ? su.k_data : k;
+    const bool gc_mode = kd < k;
+    std::vector<uint64_t> runs{0}, runs_t{0};
+    for (int s = 0; s < kd; s++) runs.push_back(runs.back() + srcs[s].n_parts);
+    for (int s = kd; s < k; s++) runs_t.push_back(runs_t.back() + srcs[s].n_parts);
+    const uint64_t data_parts = runs.back();
+    MRec* d_sorted = merge_sorted_runs(d_recs_a.as<MRec>(), d_recs_b.as<MRec>(), runs, stream, lut);
+    TR("merge issued");
+
+    // ---- group heads + starts ----
+    Groups groups;
+    find_groups(groups, d_sorted, data_parts, lut, stream);
+    const uint64_t n_groups = groups.n;
+    TR("groups known");
+    check_cancel(job);
+
+    // ---- reconcile + purge ----
+    std::vector<uint32_t> bases(k);  // read by an async copy: lives past the next sync
+    for (int s = 0; s < k; s++) bases[s] = srcs[s].rec_base;
+    DevBuf d_srcbases;
+    upload(d_srcbases, bases.data(), bases.size(), stream);
+    scan_group_rows(groups, d_srcbases, parsed.pc, stream);
+    TR("out rows scanned");
+    Reconciled rec;
+    rec.alloc(groups, sch, parsed.total_cpx, stream);
+    DevBuf d_tomb, d_ctr_arena;
+    uint64_t ctr_arena_cap = 0;
+    if (sch.counters) {
+        ctr_arena_cap = counter_arena_cap(parsed, sch.n_cols, stream);
+        d_ctr_arena.alloc(ctr_arena_cap);
+        sch.ctr_arena = d_ctr_arena.as<uint8_t>();
+    }
+    const uint32_t tomb_cap = tomb_list_cap(groups.total_rows, parsed.total_cpx, n_groups, sch);
+    d_tomb.alloc((uint64_t)tomb_cap * 4);
+    MerkleLeaves merkle;
+    PurgeInputs purge;
+    const int32_t* group_leaf =
+        mode.merkle ? merkle.assign(*mode.merkle->spec, groups, stream) : nullptr;
+    PurgeParams2 pp = purge.build(job, sw, stream);
+    pp.group_leaf = group_leaf;
+    HIP_CHECK(hipEventRecord(ev.er0, stream));
+    // GC mode: purge is DEFERRED until after the garbage filter
+    PurgeParams2 pp_data = pp;
+    if (gc_mode) {
+        pp_data.gc_before = INT64_MIN;
+        pp_data.never_purge = 1;
+        pp_data.enforce_strict_liveness = 0;
+    }
+    launch_reconcile(groups, kd, d_srcbases, parsed, rec, sch, pp_data, d_error, stream);
+    HIP_CHECK(hipEventRecord(ev.er1, stream));
+    HIP_CHECK(hipEventRecord(ev.e4, stream));
+    TR("reconcile issued");
+    if (unsigned long long err = read_dev_error(d_error, stream))
+        throw std::runtime_error("GPU reconcile error code " + std::to_string(err));
+
+    // ---- garbage collect: merge the tombstone sources, filter, purge ----
+    GarbageCollect gc;
+    const bool gc_ran = gc_mode && n_groups > 0;
+    if (gc_ran) {
+        gc.run(job, runs_t, d_recs_a.as<MRec>() + data_parts, d_recs_b.as<MRec>() + data_parts, lut,
+               d_srcbases, parsed, sch, ctr_arena_cap, pp, pp_data, rec, n_groups, d_error, stream);
+        TR("garbage filtered");
+    }
+
+    // ---- output header, then the mode's epilogue ----
+    const MergedOutput out{rec.parts, gc_ran ? gc.rows : rec.rows, n_groups,
+                           SerParams2{merged_header_stats(su.stats, kd), sch},
+                           rec.stats, d_tomb, tomb_cap};
+    restore_ck_ascending(out.parts.op, out.rows, n_groups, sch, stream);
+    if (mode.digest_path || mode.merkle) {
+        // digests instead of a written sstable: no writer, so no phase times
+        // and no merged_counts either
+        uint64_t cnt;
+        if (mode.merkle) {
+            cnt = merkle.reduce(*mode.merkle, su.js.header, sch, out.parts.op, out.rows, n_groups,
+                                stream);
+        } else {
+            cnt = write_digest_file(mode.digest_path, su.js.header, sch, out.parts.op, out.rows,
+                                    n_groups, stream);
+            if (mode.digest_count) *mode.digest_count = cnt;
+        }
+        std::lock_guard<std::mutex> gl(res_mu);
+        res->partitions_out += cnt;
+        return;
+    }
+    const OutputOptions oopt{sw.out_base, su.cinfos[0].snappy, su.bti, su.out_chunk_len, sw.wslot};
+    const WriteDeviceOut w = mode.route
+        ? write_routed_outputs(job, *mode.route, out, su.js.header, oopt, stream)
+        : write_plain_or_split(job, su, kd, out, oopt, stream);
+    TR("writer done");
+    account_result(res, res_mu, ev, w, rec.stats);
+}
 
 
 // ---------------------------------------------------------------------------
@@ -2444,20 +2508,14 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
     int k = job->n_inputs + (job->n_tomb_sources > 0 ? job->n_tomb_sources : 0);
     su.k = k;
     {
-        auto exists = [](const std::string& p2) {
-            FILE* f = fopen(p2.c_str(), "rb");
-            if (f) fclose(f);
-            return f != nullptr;
-        };
         std::string b0 = job->input_bases[0];
-        su.bti = exists(b0 + "-Partitions.db") && !exists(b0 + "-Index.db");
+        su.bti = file_exists(b0 + "-Partitions.db") && !file_exists(b0 + "-Index.db");
     }
     su.k_data = job->n_inputs;
     su.in_bases.resize(k);
     su.index_data.resize(k);
     su.cinfos.resize(k);
     su.stats.resize(k);
-    su.generations.resize(k);
     su.positions.resize(k);
     su.entry_offs.resize(k);
     su.bti_prefixes.resize(k);
@@ -2507,8 +2565,7 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
     }
     {
         std::vector<std::thread> mth;
-        std::vector<std::string> merr(k);
-        std::vector<int> mkind(k, 0);  // 1 unsupported, 2 format (keeps the ABI code)
+        std::vector<std::exception_ptr> merr(k);  // rethrown as thrown: keeps the ABI code
         for (int s = 0; s < k; s++) {
             su.in_bases[s] = s < su.k_data ? job->input_bases[s]
                                            : job->tombstone_source_bases[s - su.k_data];
@@ -2541,28 +2598,17 @@ static void compact_setup(const gpuc_job* job, CompactSetup& su, bool preread_fu
                     su.cinfos[s] = parse_compression_info(read_file(base + "-CompressionInfo.db"));
                     su.stats[s] = parse_statistics(read_file(base + "-Statistics.db"));
                     if (!preread_full) su.comp_file_sz[s] = file_size_of(base + "-Data.db");
-                } catch (const unsupported_error& e) { merr[s] = e.what(); mkind[s] = 1;
-                } catch (const format_error& e) { merr[s] = e.what(); mkind[s] = 2;
-                } catch (const std::exception& e) { merr[s] = e.what(); }
+                } catch (const std::exception&) { merr[s] = std::current_exception(); }
             });
         }
         for (auto& t : mth) t.join();
         for (int s = 0; s < k; s++)
-            if (!merr[s].empty()) {
-                if (mkind[s] == 1) throw unsupported_error(merr[s]);
-                if (mkind[s] == 2) throw format_error(merr[s]);
-                throw std::runtime_error(merr[s]);
-            }
+            if (merr[s]) std::rethrow_exception(merr[s]);
     }
     for (int s = 0; s < k; s++) {
-        const std::string& base = su.in_bases[s];
         auto& st = su.stats[s];
         if (!st.partitioner.empty() && st.partitioner.find("Murmur3") == std::string::npos)
             throw std::runtime_error("Murmur3Partitioner required");
-        size_t sl = base.rfind('/');
-        std::string name = sl == std::string::npos ? base : base.substr(sl + 1);
-        size_t a = name.find('-'), b2 = name.find('-', a + 1);
-        su.generations[s] = std::stoull(name.substr(a + 1, b2 - a - 1));
     }
     su.js = resolve_job_schema(su.stats, su.k_data);
     if (su.bti) refuse_bti_desc(su.js.header.clustering_types, "a `da` (BTI) input");
@@ -2591,16 +2637,18 @@ static int64_t index_entry_token(const bytes& ib, uint64_t off) {
     return murmur3_token(ib.data() + off + 2, klen);
 }
 
-extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
+// The run behind gpuc_compact, gpuc_validate, gpuc_validate_merkle and
+// gpuc_compact_routed: `mode` says what it produces. The mode entry points
+// reject the job options they cannot be combined with before calling this.
+static int run_compaction(const gpuc_job* job, gpuc_result* res, const CompactMode& mode) {
     memset(res, 0, sizeof(*res));
-    double t_start_all;
-    auto wall = []() {
-        struct timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
+    const double t_start_all = wall_ms();
+    if (g_trace) g_trace_t0 = wall_ms();
+    auto failed = [&](int code, const std::exception& e) {
+        set_err(res->error, sizeof(res->error), e.what());
+        res->ms_total = wall_ms() - t_start_all;
+        return code;
     };
-    t_start_all = wall();
-    if (g_trace) g_trace_t0 = trace_wall();
     try {
         int ndev = gpuc_device_count();
         if (ndev <= 0) { set_err(res->error, sizeof(res->error), "no HIP device (no CPU fallback)"); return GPUC_ERR_NO_GPU; }
@@ -2617,14 +2665,14 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
         (void)checked_chunk_len_arg(job->output_chunk_length, CHUNK_LEN);
         if (job->max_output_bytes && job->n_output_shards > 1)
             throw unsupported_error("max_output_bytes + n_output_shards unsupported");
-        double t0 = wall();
+        double t0 = wall_ms();
         int S_pre = job->n_output_shards > 1 ? job->n_output_shards : 1;
         CompactSetup su;
         compact_setup(job, su, S_pre == 1);
         // 0 == the chunk length of input_bases[0] (what the reference
         // compactor does when the table params are unchanged)
         su.out_chunk_len = checked_chunk_len_arg(job->output_chunk_length, su.cinfos[0].chunk_len);
-        res->ms_read_io = wall() - t0;
+        res->ms_read_io = wall_ms() - t0;
         TR("meta+index parsed");
         for (int s = 0; s < su.k_data; s++)
             res->input_uncompressed_bytes += su.cinfos[s].data_len;
@@ -2635,10 +2683,11 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
         if (S > 1024) throw std::runtime_error("n_output_shards must be <= 1024");
         std::mutex res_mu;
         if (S == 1) {
-            std::vector<std::pair<uint32_t, uint32_t>> pr(su.k);
+            ShardWindow sw;
             for (int s = 0; s < su.k; s++)
-                pr[s] = {0u, (uint32_t)(su.positions[s].size() - 1)};
-            compact_one(job, su, pr, job->output_base, 0, res, res_mu);
+                sw.pr.push_back({0u, (uint32_t)(su.positions[s].size() - 1)});
+            sw.out_base = job->output_base;
+            compact_one(job, su, sw, mode, res, res_mu);
         } else {
             if (job->has_token_range)
                 throw std::runtime_error("token_range + n_output_shards unsupported");
@@ -2720,22 +2769,30 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
             // two workers: front-phase kernels of one shard overlap the
             // other shard's compress
             std::atomic<int> next{0};
+            // a worker's failure: a cancellation keeps its type; any other
+            // error is rethrown by message as a plain runtime error
             std::vector<std::string> werr(2);
+            bool wcancelled[2] = {false, false};
             auto workfn = [&](int w) {
                 for (;;) {
                     int i = next.fetch_add(1);
                     if (i >= S) break;
-                    std::vector<std::pair<uint32_t, uint32_t>> pr(su.k);
+                    ShardWindow sw;
                     for (int s = 0; s < su.k; s++) {
                         // bti: window = [left-biased start, right-biased end)
                         uint32_t e2 = su.bti ? boundsR[s][i + 1] : bounds[s][i + 1];
-                        pr[s] = {std::min(bounds[s][i], e2), e2};
+                        sw.pr.push_back({std::min(bounds[s][i], e2), e2});
                     }
-                    std::string out_i = dir + "/" + pre + std::to_string(gen0 + i) + post;
-                    int64_t sh_lo = lo_tok[i];
-                    int64_t sh_hi = i + 1 < S ? lo_tok[i + 1] - 1 : INT64_MAX;
+                    sw.out_base = dir + "/" + pre + std::to_string(gen0 + i) + post;
+                    sw.wslot = w;
+                    sw.exact = su.bti;
+                    sw.tok_lo = lo_tok[i];
+                    sw.tok_hi = i + 1 < S ? lo_tok[i + 1] - 1 : INT64_MAX;
                     try {
-                        compact_one(job, su, pr, out_i, w, res, res_mu, su.bti, sh_lo, sh_hi);
+                        compact_one(job, su, sw, mode, res, res_mu);
+                    } catch (const cancelled_error&) {
+                        wcancelled[w] = true;
+                        break;
                     } catch (const std::exception& e) {
                         werr[w] = e.what();
                         break;
@@ -2745,33 +2802,23 @@ extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
             std::thread w0(workfn, 0), w1(workfn, 1);
             w0.join();
             w1.join();
-            for (auto& e : werr)
-                if (!e.empty()) {
-                    if (e.find("cancel_flag set") != std::string::npos) throw cancelled_error();
-                    throw std::runtime_error(e);
-                }
+            for (int w = 0; w < 2; w++) {
+                if (wcancelled[w]) throw cancelled_error();
+                if (!werr[w].empty()) throw std::runtime_error(werr[w]);
+            }
         }
-        res->ms_total = wall() - t_start_all;
+        res->ms_total = wall_ms() - t_start_all;
         return GPUC_OK;
-    } catch (const cancelled_error& e) {
-        set_err(res->error, sizeof(res->error), e.what());
-        res->ms_total = wall() - t_start_all;
-        return GPUC_ERR_CANCELLED;
-    } catch (const unsupported_error& e) {
-        set_err(res->error, sizeof(res->error), e.what());
-        res->ms_total = wall() - t_start_all;
-        return GPUC_ERR_UNSUPPORTED;
-    } catch (const format_error& e) {
-        set_err(res->error, sizeof(res->error), e.what());
-        res->ms_total = wall() - t_start_all;
-        return GPUC_ERR_FORMAT;
-    } catch (const std::exception& e) {
-        set_err(res->error, sizeof(res->error), e.what());
-        res->ms_total = wall() - t_start_all;
-        return GPUC_ERR_INTERNAL;
+    } catch (const cancelled_error& e) { return failed(GPUC_ERR_CANCELLED, e);
+    } catch (const unsupported_error& e) { return failed(GPUC_ERR_UNSUPPORTED, e);
+    } catch (const format_error& e) { return failed(GPUC_ERR_FORMAT, e);
+    } catch (const std::exception& e) { return failed(GPUC_ERR_INTERNAL, e);
     }
 }
 
+extern "C" int gpuc_compact(const gpuc_job* job, gpuc_result* res) {
+    return run_compaction(job, res, CompactMode{});
+}
 
 // One-sstable verification (Verifier.java / `nodetool verify --extended`
 // semantics): CompressionInfo + per-chunk CRC32 (verified inside the
@@ -2787,8 +2834,7 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
         Stream stream;
         ensure_crc_tables(stream);
         std::string base = input_base;
-        auto exists = [](const std::string& p) { return access(p.c_str(), F_OK) == 0; };
-        const bool da = exists(base + "-Partitions.db") && !exists(base + "-Index.db");
+        const bool da = file_exists(base + "-Partitions.db") && !file_exists(base + "-Index.db");
         HCompressionInfo ci = parse_compression_info(read_file(base + "-CompressionInfo.db"));
         HStatistics st = parse_statistics(read_file(base + "-Statistics.db"));
         if (da) refuse_bti_desc(st.clustering_types, "a `da` (BTI) input");
@@ -2837,9 +2883,7 @@ extern "C" int gpuc_verify(const char* input_base, int32_t device, char* error,
 
         // GPU: decompress (chunk CRC verify) + structural walk + order + bloom
         DevBuf d_pos, d_error, d_recs;
-        d_pos.alloc(positions.size() * 8);
-        HIP_CHECK(hipMemcpyAsync(d_pos.p, positions.data(), positions.size() * 8,
-                                 hipMemcpyHostToDevice, stream));
+        upload(d_pos, positions.data(), positions.size(), stream);
         d_error.alloc(8);
         HIP_CHECK(hipMemsetAsync(d_error.p, 0, 8, stream));
         DecodedFile dec;
@@ -3670,9 +3714,9 @@ extern "C" int gpuc_validate_merkle(const gpuc_job* job, const gpuc_merkle_spec*
     MerkleRun run{spec, leaf_hash, leaf_partitions, 0};
     gpuc_job vjob = *job;
     if (!vjob.output_base) vjob.output_base = "/unused";  // nothing is written
-    g_merkle = &run;
-    int rc = gpuc_compact(&vjob, &res);
-    g_merkle = nullptr;
+    CompactMode mode;
+    mode.merkle = &run;
+    int rc = run_compaction(&vjob, &res, mode);
     if (rc == GPUC_OK && n_partitions) *n_partitions = run.n_partitions;
     if (rc != GPUC_OK) set_err(error, error_len, res.error);
     return rc;
@@ -3695,21 +3739,21 @@ extern "C" int gpuc_compact_routed(const gpuc_job* job, const gpuc_route_spec* s
     RouteRun run{spec, outputs};
     gpuc_job rjob = *job;
     rjob.output_base = spec->output_bases[0];  // unused: every output has its own base
-    g_route = &run;
-    int rc = gpuc_compact(&rjob, res);
-    g_route = nullptr;
-    return rc;
+    CompactMode mode;
+    mode.route = &run;
+    return run_compaction(&rjob, res, mode);
 }
 
 extern "C" int gpuc_validate(const gpuc_job* job, const char* out_path, uint64_t* n_partitions,
                              char* error, size_t error_len) {
     if (validate_mode_rejected(job, error, error_len)) return GPUC_ERR_UNSUPPORTED;
     gpuc_result res{};
-    g_validate_out = out_path;
-    g_validate_count = 0;
-    int rc = gpuc_compact(job, &res);
-    g_validate_out = nullptr;
-    if (rc == GPUC_OK && n_partitions) *n_partitions = g_validate_count;
+    uint64_t count = 0;
+    CompactMode mode;
+    mode.digest_path = out_path;
+    mode.digest_count = &count;
+    int rc = run_compaction(job, &res, mode);
+    if (rc == GPUC_OK && n_partitions) *n_partitions = count;
     if (rc != GPUC_OK) set_err(error, error_len, res.error);
     return rc;
 }
